@@ -20,9 +20,19 @@ scaling: one 134,217,728-record fixed-256 batch split over the ranks with shard.
 encode-only and encode + the RCCL gather of the encoded shards to rank 0 (sbe_gather_encoded),
 each with absolute rec/s and its fraction of the HBM / xGMI roofline.
 
-Prints ONE JSON line on rank 0 with the roofline of the dominant kernel (SURVEY §8(d)'s
-algorithmic bytes per launch ÷ its average duration from HIP events on the launch stream) and the
-CPU baseline (the oracle restatement, OpenMP, timed on a bounded sample on rank 0 at N=1).
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set up, settle and
+warm up, time the K steps, write the outputs (--dump-outputs) and print `metric`, `value`, `unit`,
+`ms_per_step` and the configuration.  `--full` adds everything else to the same line, each in
+passes of its own after the timed region: the roofline of the dominant kernel (SURVEY §8(d)'s
+algorithmic bytes per launch ÷ its average duration from HIP events on the launch stream), the
+warm-cache figure, whole-call encode / decode times, the config-5 leg and the CPU baseline (the
+oracle restatement, OpenMP, timed on a bounded sample on rank 0 at N=1).
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32 /
+float64 holding exact integers: the encoded records, offsets and statuses and the decoded
+descriptors of a fixed, seeded sample of records, and byte sums over the whole encoded stream.  The
+inputs are seeded and timed step k always uses set k mod S, so two runs with the same arguments
+write the same files.
 """
 from __future__ import annotations
 
@@ -67,12 +77,20 @@ def parse_args():
                    help="distinct input / output buffer sets the steps rotate over (step k uses set k mod S). "
                         "Three 1 M-record sets put ~1.7 GB of other traffic between two reads of one set, so no "
                         "step finds its inputs in the 256 MB MALL; --sets 1 is the old warm-cache workload")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure what the headline does not need: the roofline "
+                        "(sampled pass, HIP events on every pack / decode dispatch, and in-region samples), the "
+                        "warm-cache pass, whole-call encode / decode times, config 5 and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy: a fixed, seeded "
+                        "sample of records (encoded bytes, offsets, statuses, decoded descriptors) and byte "
+                        "sums over the whole encoded stream, float32 / float64, under 64 MB in all")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (rank 0, --full)")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="host threads of the CPU baseline (0: the cores this process may use, capped by "
                         "OMP_NUM_THREADS, which the GPU box sets to its 16-core share)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-config5", action="store_true", help="skip the config-5 strong-scaling leg")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-config5", action="store_true", help="with --full: skip the config-5 strong-scaling leg")
     p.add_argument("--config5-records", type=int, default=134_217_728)
     p.add_argument("--config5-steps", type=int, default=3)
     p.add_argument("--separate-seq", action="store_true",
@@ -81,13 +99,18 @@ def parse_args():
     p.add_argument("--settle-ms", type=float, default=500.0,
                    help="untimed round trips before the warmup steps, until the GPU has run this long")
     p.add_argument("--event-every", type=int, default=10,
-                   help="HIP events on the pack / decode dispatches of every k-th timed step (0: none).  "
+                   help="with --full: HIP events on the pack / decode dispatches of every k-th timed step (0: none).  "
                         "A timed dispatch costs the GPU ~5 us, so the timed region samples sparsely; the "
                         "roofline comes from the sampled pass that follows it (--sample-steps)")
     p.add_argument("--sample-steps", type=int, default=0,
-                   help="steps of the sampled pass right after the timed region, HIP events on every pack / "
+                   help="with --full: steps of the sampled pass right after the timed region, HIP events on every pack / "
                         "decode dispatch (0: max(steps, 20), at most 256)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
 
 
 def launched_distributed():
@@ -358,6 +381,70 @@ def verify_gathered(dst, dst_off, N, dev, ws, chunk=1 << 22):
             "seconds": time.perf_counter() - t0}
 
 
+DUMP_SAMPLE = 32768   # records of the seeded sample (--dump-outputs): ~39 MB of .npy files
+DUMP_SEED = 0x5EED0D
+DUMP_CHUNK = 1 << 20  # bytes per entry of encoded_chunk_sums
+
+
+def _u64_halves(t):
+    """int64 tensor holding u64 bits → float64 [..., 2]: the high and the low 32 bits, both exact."""
+    a = np.ascontiguousarray(t.cpu().numpy()).view(np.uint64)
+    return np.stack([a >> np.uint64(32), a & np.uint64(0xFFFFFFFF)], axis=-1).astype(np.float64)
+
+
+def dump_outputs(path, b, n, record_bytes=256):
+    """Write what one step left in the buffer set `b` (what a caller of encode_topic_batch +
+    decode_batch receives) as path/<name>.npy, every value an integer that its float type holds
+    exactly.  Per record of a fixed sample (DUMP_SAMPLE indices drawn with DUMP_SEED, sorted, the
+    first and the last record always among them):
+      sample_index f64 [k]; encoded_records f32 [k, 256] (the record's bytes, zero past its end),
+      encoded_offset, encoded_len f64 [k] (out_off[i], out_off[i+1] - out_off[i]), encode_status f32 [k];
+      decoded_status, decoded_flags f32 [k], decoded_hdr f32 [k, 4], decoded_view_off,
+      decoded_view_len f64 [k, 5], decoded_ts_hi_lo, decoded_seq_hi_lo f64 [k, 2] (u64 as two u32).
+    Over the whole batch: encoded_chunk_sums f64 (the byte sum of every DUMP_CHUNK bytes of the
+    encoded stream) and decoded_column_sums f64 [16] (status, flags, hdr[4], view_off[5], view_len[5]
+    summed over all records)."""
+    os.makedirs(path, exist_ok=True)
+    out, off, dec = b["out"], b["out_off"], b["dec"]
+    dev = out.device
+    k = min(n, DUMP_SAMPLE)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    idx[0], idx[-1] = 0, n - 1
+    i = torch.from_numpy(idx).to(dev)
+    start = off[i]
+    ln = off[i + 1] - start
+    col = torch.arange(record_bytes, device=dev)
+    pos = (start[:, None] + col[None, :]).clamp_(0, out.numel() - 1)
+    rec = out[pos] * (col[None, :] < ln[:, None]).to(torch.uint8)
+    total = min(max(int(off[n].item()), 0), out.numel())
+    whole = total // DUMP_CHUNK * DUMP_CHUNK
+    sums = [out[:whole].view(-1, DUMP_CHUNK).sum(1, dtype=torch.int64)]
+    if total > whole:
+        sums.append(out[whole:total].sum(dtype=torch.int64).reshape(1))
+    u32 = 0xFFFFFFFF
+    cols = [dec.status[:n].sum(dtype=torch.int64).reshape(1), dec.flags[:n].sum(dtype=torch.int64).reshape(1),
+            (dec.hdr[:n].to(torch.int64) & 0xFFFF).sum(0), (dec.view_off[:n].to(torch.int64) & u32).sum(0),
+            (dec.view_len[:n].to(torch.int64) & u32).sum(0)]
+    arrays = {
+        "sample_index": idx.astype(np.float64),
+        "encoded_records": rec.cpu().numpy().astype(np.float32),
+        "encoded_offset": start.cpu().numpy().astype(np.float64),
+        "encoded_len": ln.cpu().numpy().astype(np.float64),
+        "encode_status": b["status"][i].cpu().numpy().astype(np.float32),
+        "encoded_chunk_sums": torch.cat(sums).cpu().numpy().astype(np.float64),
+        "decoded_status": dec.status[i].cpu().numpy().astype(np.float32),
+        "decoded_flags": dec.flags[i].cpu().numpy().astype(np.float32),
+        "decoded_hdr": dec.hdr[i].cpu().numpy().view(np.uint16).astype(np.float32),
+        "decoded_view_off": dec.view_off[i].cpu().numpy().view(np.uint32).astype(np.float64),
+        "decoded_view_len": dec.view_len[i].cpu().numpy().view(np.uint32).astype(np.float64),
+        "decoded_ts_hi_lo": _u64_halves(dec.ts[i]),
+        "decoded_seq_hi_lo": _u64_halves(b["seq"][i]),
+        "decoded_column_sums": torch.cat(cols).cpu().numpy().astype(np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
     if args.sample_steps <= 0:
@@ -383,8 +470,11 @@ def main():
     ws = sbecodec.alloc_workspace(n, dev)
     stream = torch.cuda.current_stream()
 
-    ev_enc = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    ev_dec = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    full = args.full
+    event_every = args.event_every if full else 0  # a plain run times no dispatch
+    n_ev = args.steps if full else 0  # torch events of the whole-call pass (--full)
+    ev_enc = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
+    ev_dec = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
     rot = {"i": 0, "only": None}  # next set; "only": pin every step to one set (the warm-cache pass)
 
     def step(k=None):
@@ -421,7 +511,7 @@ def main():
     # host-side setup before the warmup, so the GPU goes from the warmup steps straight into the
     # timed ones: creating the profiling events takes ~1 ms of host time, during which an idle GPU
     # lowers its clocks
-    sbecodec.profile_enable(args.event_every)  # events on the pack / decode dispatches
+    sbecodec.profile_enable(event_every)  # events on the pack / decode dispatches
     # settle: untimed round trips until the GPU has run the workload for settle_ms (its clocks ramp
     # up over the first tens of milliseconds of sustained load; a 5-step warmup is ~1 ms), then the
     # W warmup steps, then the timed K steps, with no host gap in between
@@ -433,9 +523,15 @@ def main():
         torch.cuda.synchronize()
         if (time.perf_counter() - t_set) * 1e3 >= args.settle_ms:
             break
+    # the settle loop ends on the clock, so its step count differs from run to run: up to S - 1 more
+    # untimed steps bring the rotation to where timed step k uses set k mod S in every run (the last
+    # timed step's outputs, --dump-outputs, are then the same set's), with the rotation unbroken
+    while (rot["i"] + args.warmup) % nsets:
+        step()
+        settle_steps += 1
     for _ in range(args.warmup):
         step()
-    sbecodec.profile_enable(args.event_every)  # restart the rings: warmup launches are not sampled
+    sbecodec.profile_enable(event_every)  # restart the rings: warmup launches are not sampled
     barrier(world)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -444,6 +540,37 @@ def main():
     torch.cuda.synchronize()
     barrier(world)
     el = max_over_ranks(time.perf_counter() - t0, world)
+    total = n * world * args.steps
+    value = total / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sets[(args.steps - 1) % nsets], n)
+    line = {
+        "metric": METRIC, "value": value, "unit": "records/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic", "full": full,
+        "config": {"workload": "roundtrip_fixed256_orders", "records_per_gpu": n, "record_bytes": 256,
+                   "encode": "wire-correct TopicMessage, packed SoA input",
+                   "decode": "parse_message descriptors (views) + sequence_number evaluation",
+                   "parallelism": f"shard{world}", "settle": {"ms": args.settle_ms, "steps": settle_steps},
+                   "input_sets": nsets,
+                   "rotation": (f"step k encodes set k mod {nsets} and decodes that set's stream; every set has "
+                                f"its own inputs and outputs ({nsets} x ~{(n * (250 + 256 + 58 + 17)) / 1e9:.2f} GB)")},
+    }
+    if args.dump_outputs:
+        line["dump_outputs"] = args.dump_outputs
+    if full:
+        line.update(full_passes(args, world, rank, dev, n, sets, step, rot, ev_enc, ev_dec))
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if dist_on():
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def full_passes(args, world, rank, dev, n, sets, step, rot, ev_enc, ev_dec):
+    """--full: everything the line reports beyond the headline, measured after the timed region in
+    passes of their own.  Returns the extra keys of the result line (rank 0; {} on the others)."""
+    nsets = len(sets)
     # the in-region samples (every event_every-th step), then the sampled pass: the same steps on
     # the same stream right after the timed region, HIP events on every pack / decode dispatch
     # (hipExtLaunchKernel timestamps of the kernel itself); its mean is the roofline's duration
@@ -477,8 +604,6 @@ def main():
     torch.cuda.synchronize()
     enc_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_enc]))
     dec_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_dec]))
-    total = n * world * args.steps
-    value = total / el
 
     c5 = None
     if not args.no_config5:
@@ -505,16 +630,6 @@ def main():
             cpu = cpu_baseline(min(n, 200_000), args.cpu_seconds, args.cpu_threads or default_cpu_threads())
         ach = gbs(dom["bytes_per_record"], dom["ms"])
         line = {
-            "metric": METRIC, "value": value, "unit": "records/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": "roundtrip_fixed256_orders", "records_per_gpu": n, "record_bytes": 256,
-                       "encode": "wire-correct TopicMessage, packed SoA input",
-                       "decode": "parse_message descriptors (views) + sequence_number evaluation",
-                       "parallelism": f"shard{world}", "settle": {"ms": args.settle_ms, "steps": settle_steps},
-                       "input_sets": nsets,
-                       "rotation": (f"step k encodes set k mod {nsets} and decodes that set's stream; every set has "
-                                    f"its own inputs and outputs ({nsets} x ~{(n * (250 + 256 + 58 + 17)) / 1e9:.2f} GB)")},
             "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "kernel": dom["kernel"],
                          "kernel_ms": dom["ms"], "bytes_per_record": dom["bytes_per_record"],
@@ -544,10 +659,8 @@ def main():
         }
         if c5 is not None:
             line["config5"] = c5
-        print(json.dumps(line), flush=True)
-    if dist_on():
-        import torch.distributed as dist
-        dist.destroy_process_group()
+        return line
+    return {}
 
 
 def measured_traffic(kernel, n):

@@ -6,7 +6,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=${TAG:-run}
-CMD=${CMD:-bench.py --no-config5 --no-cpu-baseline --steps 5 --warmup 2}
+CMD=${CMD:-bench.py --full --no-config5 --no-cpu-baseline --steps 5 --warmup 2}
 K=${KREGEX:-sbe_enc_pack|sbe_decode_kernel|sbe_enc_sums}
 O=gpurun_out/prof_$TAG
 mkdir -p $O
