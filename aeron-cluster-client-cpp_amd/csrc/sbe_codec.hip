@@ -4813,6 +4813,9 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
     }
 }
 
+// after every other kernel, so that this file's earlier device code keeps its place in the code object
+#include "commit_class.hpp"
+
 }  // namespace
 
 struct sbe_server {
@@ -5400,6 +5403,35 @@ int sbe_materialize_views(const uint8_t* in, const uint64_t* rec_off, uint64_t n
     hipLaunchKernelGGL(mat_scan_blocks, dim3(1), dim3(kMatBlk), 0, s, a, nb);
     const uint64_t g = SBE_MAT_PERSIST ? pack_grid(reinterpret_cast<const void*>(&mat_copy), nt) : nt;
     hipLaunchKernelGGL(mat_copy, dim3((uint32_t)g), dim3(kWave), 0, s, a, nt);
+    return record_hip(hipGetLastError());
+}
+
+size_t sbe_commit_workspace_size(uint64_t, uint32_t) { return 0; }
+
+int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                         const uint8_t* topic_arena, const uint32_t* topic_off, uint32_t k,
+                         const sbe_commit_out* out, void*, size_t, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    if (!out || !out->last || !out->count || mis(out->last, 7) || mis(out->count, 7)) return SBE_EINVAL;
+    if (k == 0 || k > SBE_COMMIT_MAX_TOPICS) return SBE_EINVAL;
+    // an empty batch only initialises last / count: its per-record arrays may be null
+    if (n && (!in || !rec_off || !dec || !dec->status || !dec->flags || !dec->view_off || !dec->view_len ||
+              !topic_arena || !topic_off || !out->cm || !out->topic_src || !out->topic_kind || !out->topic_off ||
+              !out->topic_len || !out->topic_idx))
+        return SBE_EINVAL;
+    if (n && (mis(rec_off, 7) || mis(dec->view_off, 3) || mis(dec->view_len, 3) || mis(topic_off, 3) ||
+              mis(out->topic_off, 3) || mis(out->topic_len, 3) || mis(out->topic_idx, 3)))
+        return SBE_EINVAL;
+    const uint64_t tiles = (n + kTile - 1) / kTile;
+    if (tiles > 0x7fffffffull) return SBE_EINVAL;
+    hipLaunchKernelGGL(sbe_commit_init, dim3(1), dim3(kWave), 0, s, out->last, out->count, k);
+    if (n) {
+        CmArgs a{in,           rec_off,        n,          dec->status,    dec->flags,     dec->view_off,
+                 dec->view_len, topic_arena,   topic_off,  k,              out->cm,        out->topic_src,
+                 out->topic_kind, out->topic_off, out->topic_len, out->topic_idx, out->last, out->count};
+        hipLaunchKernelGGL(sbe_commit_kernel, dim3((uint32_t)tiles), dim3(kWave), 0, s, a);
+    }
     return record_hip(hipGetLastError());
 }
 

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -1654,6 +1655,281 @@ std::vector<std::uint8_t> CommitManager::build_commit_offset_message(const std::
     if (st == 1 || st == 2) throw std::runtime_error(kLiteE109[st - 1]);
     if (st != SBE_ENC_OK) throw std::runtime_error("sbecodec: encode failed");
     return b.bytes.to_vector();
+}
+
+void CommitManager::commit_message(const std::string& topic, const std::string& message_identifier,
+                                   const std::string& message_id, std::uint64_t timestamp_nanos,
+                                   std::uint64_t sequence_number) {
+    std::lock_guard<std::mutex> lock(commits_mutex_);
+    commits_[topic + ":" + message_identifier] =
+        CommitOffset{topic, message_identifier, message_id, timestamp_nanos, sequence_number};
+}
+
+std::shared_ptr<CommitOffset> CommitManager::get_last_commit(const std::string& topic,
+                                                             const std::string& message_identifier) const {
+    std::lock_guard<std::mutex> lock(commits_mutex_);
+    auto it = commits_.find(topic + ":" + message_identifier);
+    return it == commits_.end() ? nullptr : std::make_shared<CommitOffset>(it->second);
+}
+
+std::unordered_map<std::string, CommitOffset> CommitManager::get_all_commits() const {
+    std::lock_guard<std::mutex> lock(commits_mutex_);
+    return commits_;
+}
+
+namespace {
+// Value::asString of a topic token the device located (jsoncpp 1.9.5).  These four helpers are
+// new with AutoCommitter: the mirror had no decode-side JSON code (its Order JSON is written on the
+// device).  They convert only tokens that the device reader has already parsed and validated, so
+// the string decode cannot fail here and they do not check again.
+void utf8_append(uint32_t cp, std::string& out) {
+    if (cp <= 0x7f) {
+        out += (char)cp;
+    } else if (cp <= 0x7ff) {
+        out += (char)(0xC0 | (cp >> 6));
+        out += (char)(0x80 | (cp & 0x3f));
+    } else if (cp <= 0xffff) {
+        out += (char)(0xE0 | (cp >> 12));
+        out += (char)(0x80 | ((cp >> 6) & 0x3f));
+        out += (char)(0x80 | (cp & 0x3f));
+    } else if (cp <= 0x10ffff) {
+        out += (char)(0xF0 | (cp >> 18));
+        out += (char)(0x80 | ((cp >> 12) & 0x3f));
+        out += (char)(0x80 | ((cp >> 6) & 0x3f));
+        out += (char)(0x80 | (cp & 0x3f));
+    }
+}
+// four hex digits at t[i..i+4): the device's jhex4 accepted them, so a non-hex character or a short
+// tail cannot occur and is not diagnosed (a non-hex character would be read as 'A'-based)
+uint32_t hex4(std::string_view t, size_t i) {
+    uint32_t v = 0;
+    for (size_t j = i; j < i + 4 && j < t.size(); ++j) {
+        const char c = t[j];
+        v = v * 16 + (c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c - 'A' + 10);
+    }
+    return v;
+}
+std::string json_unescape(std::string_view t) {  // OurReader::decodeString between the quotes
+    std::string out;
+    for (size_t i = 0; i < t.size();) {
+        const char c = t[i++];
+        if (c != '\\' || i == t.size()) {
+            out += c;
+            continue;
+        }
+        const char x = t[i++];
+        switch (x) {
+            case 'b': out += '\b'; break;
+            case 'f': out += '\f'; break;
+            case 'n': out += '\n'; break;
+            case 'r': out += '\r'; break;
+            case 't': out += '\t'; break;
+            case 'u': {
+                uint32_t cp = hex4(t, i);
+                i += 4;
+                if (cp >= 0xD800 && cp <= 0xDBFF) {  // a surrogate pair: "\uXXXX" follows
+                    cp = 0x10000 + ((cp & 0x3FF) << 10) + (hex4(t, i + 2) & 0x3FF);
+                    i += 6;
+                }
+                utf8_append(cp, out);
+                break;
+            }
+            default: out += x; break;  // '"', '/', '\\'
+        }
+    }
+    return out;
+}
+std::string json_number_as_string(std::string_view t) {  // decodeNumber, then valueToString
+    size_t p = 0;
+    const bool neg = !t.empty() && t[0] == '-';
+    if (neg) ++p;
+    const uint64_t maxv = neg ? (uint64_t)1 << 63 : ~0ull, thr = maxv / 10;
+    uint64_t v = 0;
+    bool real = false;
+    while (p < t.size() && !real) {
+        const char c = t[p++];
+        if (c < '0' || c > '9') {
+            real = true;
+        } else {
+            const uint64_t dg = c - '0';
+            if (v >= thr && (v > thr || p != t.size() || dg > maxv % 10)) real = true;
+            else v = v * 10 + dg;
+        }
+    }
+    if (!real) return neg ? (v ? "-" + std::to_string(v) : "0") : std::to_string(v);
+    const double d = std::strtod(std::string(t).c_str(), nullptr);
+    if (d != d) return "null";
+    if (d > DBL_MAX) return "1e+9999";
+    if (d < -DBL_MAX) return "-1e+9999";
+    char buf[40];
+    std::snprintf(buf, sizeof buf, "%.17g", d);
+    std::string s(buf);
+    if (s.find('.') == std::string::npos && s.find('e') == std::string::npos) s += ".0";
+    return s;
+}
+}  // namespace
+
+AutoCommitter::AutoCommitter(std::string client_id, std::string fallback_topic)
+    : client_id_(std::move(client_id)), fallback_(std::move(fallback_topic)) {
+    if (fallback_.size() > SBE_COMMIT_TABLE_BYTES) throw std::length_error("AutoCommitter: fallback topic too long");
+}
+
+void AutoCommitter::set_message_identifier(const std::string& topic, const std::string& identifier) {
+    if (!identifiers_.count(topic)) {
+        size_t bytes = fallback_.size() + topic.size();
+        for (const auto& kv : identifiers_) bytes += kv.first.size();
+        if (identifiers_.size() + 2 > SBE_COMMIT_MAX_TOPICS || bytes > SBE_COMMIT_TABLE_BYTES)
+            throw std::length_error("AutoCommitter: the topic table holds 64 topics and 4096 bytes");
+    }
+    identifiers_[topic] = identifier;
+}
+
+const std::string& AutoCommitter::message_identifier(const std::string& topic) const {
+    auto it = identifiers_.find(topic);
+    return it == identifiers_.end() ? client_id_ : it->second;
+}
+
+CommitPlan AutoCommitter::classify(const ParsedBatch& batch) const {
+    const size_t n = batch.n_;
+    CommitPlan plan;
+    plan.table.push_back(fallback_);
+    for (const auto& kv : identifiers_) plan.table.push_back(kv.first);
+    const uint32_t k = (uint32_t)plan.table.size();
+    plan.cm.resize(n);
+    plan.topic_src.resize(n);
+    plan.topic_kind.resize(n);
+    plan.topic_off.resize(n);
+    plan.topic_len.resize(n);
+    plan.topic_idx.resize(n);
+    plan.last.assign(k, ~0ull);
+    plan.count.assign(k + 2, 0);
+    if (n == 0) return plan;
+    const Descriptors& d = *batch.desc_;
+    const uint64_t lo = batch.rec_off_[0], bytes = batch.rec_off_[n] - lo;
+    // staged inputs: offsets (rebased), status, flags, view offsets and lengths, the table, the records
+    const size_t o_st = al16((n + 1) * 8), o_fl = o_st + al16(n), o_vo = o_fl + al16(n), o_vl = o_vo + al16(20 * n),
+                 o_ta = o_vl + al16(20 * n), o_to = o_ta + SBE_COMMIT_TABLE_BYTES,
+                 o_data = o_to + al16(4 * (SBE_COMMIT_MAX_TOPICS + 1)), stage = o_data + (size_t)bytes + 16;
+    Ctx& c = ctx();
+    Pipeline::Slot& s = c.pipe.slot[0];  // serial use of the pipeline's first slot (idle between calls)
+    hipStream_t stream = c.batch_stream();
+    s.pin.need(stage);
+    uint8_t* hp = s.pin.b();
+    uint64_t* ro = reinterpret_cast<uint64_t*>(hp);
+    uint32_t* vo = reinterpret_cast<uint32_t*>(hp + o_vo);
+    uint32_t* vl = reinterpret_cast<uint32_t*>(hp + o_vl);
+    ro[n] = bytes;
+    for_ranges(n, 4096, [&](size_t x, size_t y) {
+        for (size_t i = x; i < y; ++i) {
+            ro[i] = batch.rec_off_[i] - lo;
+            hp[o_st + i] = d.status(i);
+            hp[o_fl + i] = d.flags(i);
+            std::memcpy(vo + 5 * i, d.off(i), 20);
+            std::memcpy(vl + 5 * i, d.len(i), 20);
+        }
+    });
+    std::memset(hp + o_ta, 0, SBE_COMMIT_TABLE_BYTES);
+    uint32_t* to = reinterpret_cast<uint32_t*>(hp + o_to);
+    to[0] = 0;
+    for (uint32_t j = 0; j < k; ++j) {
+        std::memcpy(hp + o_ta + to[j], plan.table[j].data(), plan.table[j].size());
+        to[j + 1] = to[j] + (uint32_t)plan.table[j].size();
+    }
+    if (bytes)
+        for_ranges((size_t)bytes, size_t(1) << 18, [&](size_t x, size_t y) {
+            std::memcpy(hp + o_data + x, batch.data_ + lo + x, y - x);
+        });
+    s.d_in.need(stage);
+    const size_t p_src = al16(n), p_kind = p_src + al16(n), p_off = p_kind + al16(n), p_len = p_off + al16(4 * n),
+                 p_idx = p_len + al16(4 * n), p_last = p_idx + al16(4 * n), p_cnt = p_last + 8 * SBE_COMMIT_MAX_TOPICS,
+                 outb = p_cnt + 8 * (SBE_COMMIT_MAX_TOPICS + 2);
+    s.d_out.need(outb);
+    hip_check(hipMemcpyAsync(s.d_in.p, hp, stage, hipMemcpyHostToDevice, stream), "H2D");
+    uint8_t* di = s.d_in.b();
+    uint8_t* dq = s.d_out.b();
+    sbe_decoded dec{di + o_st, di + o_fl, nullptr, nullptr, reinterpret_cast<uint32_t*>(di + o_vo),
+                    reinterpret_cast<uint32_t*>(di + o_vl), nullptr};
+    sbe_commit_out out{dq,
+                       dq + p_src,
+                       dq + p_kind,
+                       reinterpret_cast<uint32_t*>(dq + p_off),
+                       reinterpret_cast<uint32_t*>(dq + p_len),
+                       reinterpret_cast<uint32_t*>(dq + p_idx),
+                       reinterpret_cast<uint64_t*>(dq + p_last),
+                       reinterpret_cast<uint64_t*>(dq + p_cnt)};
+    if (sbe_classify_commits(di + o_data, reinterpret_cast<const uint64_t*>(di), n, &dec, di + o_ta,
+                             reinterpret_cast<const uint32_t*>(di + o_to), k, &out, nullptr, 0, stream) != SBE_OK) {
+        c.abort_all();
+        fail("sbe_classify_commits");
+    }
+    auto back = [&](void* dst, size_t off, size_t len) {
+        hip_check(hipMemcpyAsync(dst, dq + off, len, hipMemcpyDeviceToHost, stream), "D2H");
+    };
+    back(plan.cm.data(), 0, n);
+    back(plan.topic_src.data(), p_src, n);
+    back(plan.topic_kind.data(), p_kind, n);
+    back(plan.topic_off.data(), p_off, 4 * n);
+    back(plan.topic_len.data(), p_len, 4 * n);
+    back(plan.topic_idx.data(), p_idx, 4 * n);
+    back(plan.last.data(), p_last, 8 * k);
+    back(plan.count.data(), p_cnt, 8 * (k + 2));
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    return plan;
+}
+
+std::string AutoCommitter::topic(const ParsedBatch& batch, const CommitPlan& plan, std::size_t i) const {
+    if (plan.topic_src[i] == SBE_TOPIC_SRC_FALLBACK || plan.topic_src[i] == SBE_TOPIC_SRC_NONE) return fallback_;
+    const std::string_view tok(reinterpret_cast<const char*>(batch.data_ + batch.rec_off_[i]) + plan.topic_off[i],
+                               plan.topic_len[i]);
+    switch (plan.topic_kind[i]) {
+        case SBE_TOPIC_KIND_STRING: return std::string(tok);
+        case SBE_TOPIC_KIND_STRING_ESC: return json_unescape(tok);
+        case SBE_TOPIC_KIND_NUMBER: return json_number_as_string(tok);
+        case SBE_TOPIC_KIND_TRUE: return "true";
+        case SBE_TOPIC_KIND_FALSE: return "false";
+        default: return "";  // null
+    }
+}
+
+std::size_t AutoCommitter::commit_record_by_record(const ParsedBatch& batch, const CommitPlan& plan,
+                                                   CommitManager& commits, const std::vector<bool>* callback_ok) const {
+    std::size_t calls = 0;
+    for (std::size_t i = 0; i < batch.size(); ++i) {
+        if (plan.cm[i] != SBE_CM_COMMIT || (callback_ok && !(*callback_ok)[i])) continue;
+        const std::string t = topic(batch, plan, i);
+        commits.commit_message(t, message_identifier(t), std::string(batch.view(i, 2)),
+                               (std::uint64_t)batch.timestamp(i), batch.sequence_number(i));
+        ++calls;
+    }
+    return calls;
+}
+
+std::size_t AutoCommitter::commit_batch(const ParsedBatch& batch, const CommitPlan& plan, CommitManager& commits,
+                                        const std::vector<bool>* callback_ok) const {
+    if (callback_ok) {
+        if (callback_ok->size() != batch.size()) throw std::invalid_argument("AutoCommitter: one callback result per record");
+        return commit_record_by_record(batch, plan, commits, callback_ok);
+    }
+    // the last committable record of every table entry, and every record the table does not
+    // resolve, in record order (two topics can spell one "topic:identifier" key)
+    std::vector<std::size_t> todo;
+    for (std::size_t j = 0; j < plan.last.size(); ++j)
+        if (plan.last[j] != ~0ull) todo.push_back((std::size_t)plan.last[j]);
+    if (plan.count[plan.last.size()] + plan.count[plan.last.size() + 1])
+        for (std::size_t i = 0; i < batch.size(); ++i)
+            if (plan.cm[i] == SBE_CM_COMMIT && plan.topic_idx[i] >= SBE_TOPIC_HOST) todo.push_back(i);
+    std::sort(todo.begin(), todo.end());
+    for (std::size_t i : todo) {
+        const std::string t = plan.topic_idx[i] < plan.table.size() ? plan.table[plan.topic_idx[i]] : topic(batch, plan, i);
+        commits.commit_message(t, message_identifier(t), std::string(batch.view(i, 2)),
+                               (std::uint64_t)batch.timestamp(i), batch.sequence_number(i));
+    }
+    return todo.size();
+}
+
+std::size_t AutoCommitter::commit_batch(const ParsedBatch& batch, CommitManager& commits,
+                                        const std::vector<bool>* callback_ok) const {
+    return commit_batch(batch, classify(batch), commits, callback_ok);
 }
 
 OrderJsonBatch orders_to_json(const std::vector<Order>& orders, const std::vector<std::string>& message_ids) {

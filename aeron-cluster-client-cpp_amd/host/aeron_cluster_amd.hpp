@@ -13,7 +13,10 @@
 //                                      src/session_manager.cpp:936-967, :1018-1046, :1050-1144
 //   CommitManager                      build_commit_offset_message (CommitOffsetLite),
 //                                      src/commit_manager.cpp:16-22, :107-132; CommitOffset
-//                                      include/aeron_cluster/commit_manager.hpp:17-24
+//                                      include/aeron_cluster/commit_manager.hpp:17-24; commit_message /
+//                                      get_last_commit / get_all_commits, src/commit_manager.cpp:29-51
+//   handle_incoming_message's commit   src/cluster_client.cpp:1198-1303 (should_skip_auto_commit
+//                                      :847-886, extract_topic_from_message :756-806): AutoCommitter
 //   LocalFragmentReassembler           src/cluster_client.cpp:39-82 (FragmentReassembler below)
 //   ClusterClient::offer_ingress       include/aeron_cluster/cluster_client.hpp:409 — the sink the
 //                                      encoded records are handed to (OfferFn below)
@@ -35,10 +38,13 @@
 #include <cstdint>
 #include <chrono>
 #include <functional>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <optional>
 #include <string>
 #include <string_view>
+#include <unordered_map>
 #include <vector>
 
 namespace aeron_cluster {
@@ -322,6 +328,7 @@ public:
 
 private:
     friend class MessageParser;
+    friend class AutoCommitter;
     std::shared_ptr<const detail::Descriptors> desc_;  // host copy of the device descriptors
     const std::uint8_t* data_ = nullptr;               // the caller's records (borrowed)
     const std::uint64_t* rec_off_ = nullptr;           // the caller's offsets (borrowed)
@@ -463,6 +470,63 @@ public:
                                                           const CommitOffset& offset) const;
     // Batch (one GPU launch); every offset's topic must be known.
     EncodedBatch build_commit_offset_batch(const std::vector<CommitOffset>& offsets) const;
+    // src/commit_manager.cpp:29-35: the last commit per "topic:message_identifier"
+    void commit_message(const std::string& topic, const std::string& message_identifier, const std::string& message_id,
+                        std::uint64_t timestamp_nanos, std::uint64_t sequence_number);
+    // src/commit_manager.cpp:37-46 (nullptr when there is none) and :48-51
+    std::shared_ptr<CommitOffset> get_last_commit(const std::string& topic, const std::string& message_identifier) const;
+    std::unordered_map<std::string, CommitOffset> get_all_commits() const;
+
+private:
+    mutable std::mutex commits_mutex_;
+    std::unordered_map<std::string, CommitOffset> commits_;
+};
+
+// sbe_classify_commits' outputs on the host (include/sbecodec.h: SBE_CM_*, SBE_TOPIC_*).
+struct CommitPlan {
+    std::vector<std::uint8_t> cm, topic_src, topic_kind;
+    std::vector<std::uint32_t> topic_off, topic_len, topic_idx;
+    std::vector<std::uint64_t> last, count;  // per table entry; count: + unknown, + host-resolved
+    std::vector<std::string> table;          // the topic table the plan was made with (entry 0: fallback)
+};
+
+// The commit branch of ClusterClient::handle_incoming_message (src/cluster_client.cpp:1251-1288)
+// for a whole ParsedBatch: which records commit, and under which topic, is decided on the device
+// (sbe_classify_commits: should_skip_auto_commit :847-886 and extract_topic_from_message :756-806
+// per record); the host then calls CommitManager::commit_message.  The reference keeps only the
+// last commit per "topic:identifier", so without a callback mask commit_batch commits once per
+// topic-table entry (its last committable record) and walks only the records whose topic is not
+// in the table (SBE_TOPIC_UNKNOWN) or is not a string (SBE_TOPIC_HOST: Value::asString on the
+// host), all in record order; with a mask (callback_ok[i]: the message callback of record i
+// succeeded, :1224-1239) it walks every committable record.  Either way the CommitManager ends up
+// as after the reference's sequence, record by record (commit_record_by_record).  The dedup set
+// (processed_messages_) is the caller's: it does not decide whether a record commits (:1237-1255).
+// The topic table is the fallback topic (*subscribed_topics_.begin(), or "default": the caller's,
+// since the reference's set is unordered) followed by the topics that have a stored identifier.
+class AutoCommitter {
+public:
+    explicit AutoCommitter(std::string client_id, std::string fallback_topic = "default");
+    // subscription_message_identifiers_[topic] = identifier (at most 63 topics, 4096 bytes in all
+    // with the fallback topic: std::length_error beyond that)
+    void set_message_identifier(const std::string& topic, const std::string& identifier);
+    // :1264-1278: the stored identifier of the topic, else client_id
+    const std::string& message_identifier(const std::string& topic) const;
+    // One device launch over the batch's records and descriptors.
+    CommitPlan classify(const ParsedBatch& batch) const;
+    // The topic text of record i (Value::asString of the token; the fallback topic for FALLBACK).
+    std::string topic(const ParsedBatch& batch, const CommitPlan& plan, std::size_t i) const;
+    // Commits the batch into `commits`; returns the commit_message calls made.
+    std::size_t commit_batch(const ParsedBatch& batch, CommitManager& commits,
+                             const std::vector<bool>* callback_ok = nullptr) const;
+    std::size_t commit_batch(const ParsedBatch& batch, const CommitPlan& plan, CommitManager& commits,
+                             const std::vector<bool>* callback_ok = nullptr) const;
+    // The reference's sequence: every committable record, in order.
+    std::size_t commit_record_by_record(const ParsedBatch& batch, const CommitPlan& plan, CommitManager& commits,
+                                        const std::vector<bool>* callback_ok = nullptr) const;
+
+private:
+    std::string client_id_, fallback_;
+    std::map<std::string, std::string> identifiers_;
 };
 
 // A decoded Lite record (CommitOffsetLite / OrderRequestLite / OrderNotificationLite flyweights).

@@ -13,6 +13,8 @@ Reference surface mirrored (paths relative to the reference tree):
   decode_batch(LITE)  ~ the Lite templates' generated decode flyweights
   reassemble          ~ LocalFragmentReassembler::onFragment  src/cluster_client.cpp:39-82
   decode_batch(PARSE) ~ MessageParser::parse_message        src/sbe_encoder.cpp:513-551
+  classify_commits    ~ handle_incoming_message's commit decision src/cluster_client.cpp:1198-1303
+                        (should_skip_auto_commit :847-886, extract_topic_from_message :756-806)
   decode_batch(EGRESS)~ decode_ack + MessageHandler::on_egress
                         src/ack_decoder.cpp:29-105, include/aeron_cluster/message_handler.hpp:35-68
   order_to_json_batch ~ Order::to_json src/order_types.cpp:122-181 and publish_order's headers JSON
@@ -82,6 +84,12 @@ class _Decoded(ctypes.Structure):
                 ("seq", ctypes.c_void_p)]
 
 
+class _CommitOut(ctypes.Structure):
+    _fields_ = [("cm", ctypes.c_void_p), ("topic_src", ctypes.c_void_p), ("topic_kind", ctypes.c_void_p),
+                ("topic_off", ctypes.c_void_p), ("topic_len", ctypes.c_void_p), ("topic_idx", ctypes.c_void_p),
+                ("last", ctypes.c_void_p), ("count", ctypes.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise SbeError(f"{LIB_PATH} is missing: build it with `make -C aeron-cluster-client-cpp_amd` "
@@ -140,6 +148,13 @@ def _load():
     lib.sbe_eval_sequence_numbers.restype = ctypes.c_int
     lib.sbe_eval_sequence_numbers.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                               ctypes.POINTER(_Decoded), ctypes.c_void_p, ctypes.c_void_p]
+    lib.sbe_commit_workspace_size.restype = ctypes.c_size_t
+    lib.sbe_commit_workspace_size.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+    lib.sbe_classify_commits.restype = ctypes.c_int
+    lib.sbe_classify_commits.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                         ctypes.POINTER(_Decoded), ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_uint32, ctypes.POINTER(_CommitOut), ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.c_void_p]
     lib.sbe_profile_enable.restype = ctypes.c_int
     lib.sbe_order_json_workspace_size.argtypes = [ctypes.c_uint64]
     lib.sbe_order_json_workspace_size.restype = ctypes.c_size_t
@@ -478,6 +493,85 @@ def eval_sequence_numbers(data, rec_off, dec: Decoded, seq=None, stream=None) ->
     rc = lib().sbe_eval_sequence_numbers(_ptr(data), _ptr(rec_off), n, ctypes.byref(d), _ptr(seq), _stream(stream))
     _check(rc, "sbe_eval_sequence_numbers")
     return seq[:n]
+
+
+# sbe_classify_commits: commit codes, topic sources / kinds, table sentinels (include/sbecodec.h)
+CM_COMMIT, CM_NOT_PARSED, CM_SKIP_TYPE, CM_SKIP_ACK_ID, CM_SKIP_TOPIC, CM_SKIP_CONTROL, CM_SKIP_EMPTY_PAYLOAD, \
+    CM_NO_ID = range(8)
+TOPIC_SRC_NONE, TOPIC_SRC_HEADERS, TOPIC_SRC_PAYLOAD, TOPIC_SRC_PAYLOAD_MESSAGE, TOPIC_SRC_FALLBACK = range(5)
+TOPIC_KIND_NONE, TOPIC_KIND_STRING, TOPIC_KIND_STRING_ESC, TOPIC_KIND_NUMBER, TOPIC_KIND_TRUE, TOPIC_KIND_FALSE, \
+    TOPIC_KIND_NULL = range(7)
+TOPIC_UNKNOWN = 0xFFFFFFFF
+TOPIC_HOST = 0xFFFFFFFE
+COMMIT_MAX_TOPICS = 64
+COMMIT_TABLE_BYTES = 4096
+_COMMIT_KEYS = (("cm", "uint8"), ("topic_src", "uint8"), ("topic_kind", "uint8"), ("topic_off", "uint32"),
+                ("topic_len", "uint32"), ("topic_idx", "uint32"), ("last", "uint64"), ("count", "uint64"))
+
+
+@dataclass
+class CommitPlan:
+    cm: torch.Tensor          # uint8 [n]  CM_*
+    topic_src: torch.Tensor   # uint8 [n]  TOPIC_SRC_*
+    topic_kind: torch.Tensor  # uint8 [n]  TOPIC_KIND_*
+    topic_off: torch.Tensor   # int32 [n]  (u32) topic token, relative to the record start
+    topic_len: torch.Tensor   # int32 [n]  (u32)
+    topic_idx: torch.Tensor   # int32 [n]  (u32) table entry, TOPIC_UNKNOWN or TOPIC_HOST
+    last: torch.Tensor        # int64 [k]  (u64) largest committable record index per entry, 2^64-1: none
+    count: torch.Tensor       # int64 [k+2] (u64) commits per entry, then unknown, then host-resolved
+
+    def numpy(self):
+        import numpy as np
+        return {k: getattr(self, k).cpu().numpy().view(getattr(np, t)) for k, t in _COMMIT_KEYS}
+
+
+def commit_topic_table(topics, device):
+    """The device topic table of classify_commits: (arena uint8 [COMMIT_TABLE_BYTES], off int32 [k+1])."""
+    import numpy as np
+    topics = [bytes(t) for t in topics]
+    if not 1 <= len(topics) <= COMMIT_MAX_TOPICS:
+        raise SbeError(f"classify_commits takes 1..{COMMIT_MAX_TOPICS} topics, got {len(topics)}")
+    off = np.zeros(len(topics) + 1, np.int32)
+    off[1:] = np.cumsum([len(t) for t in topics])
+    if int(off[-1]) > COMMIT_TABLE_BYTES:
+        raise SbeError(f"topic table holds {int(off[-1])} bytes, more than {COMMIT_TABLE_BYTES}")
+    arena = np.zeros(COMMIT_TABLE_BYTES, np.uint8)
+    arena[: int(off[-1])] = np.frombuffer(b"".join(topics), np.uint8)
+    return torch.from_numpy(arena).to(device), torch.from_numpy(off).to(device)
+
+
+def classify_commits(data, rec_off, dec: Decoded, topics, out: CommitPlan | None = None, stream=None) -> CommitPlan:
+    """The auto-commit decision of ClusterClient::handle_incoming_message (src/cluster_client.cpp:
+    1198-1303) for the records of a parse-mode decode_batch on the same data / rec_off: commit code,
+    extracted topic and topic-table entry per record, the last committable record and the commit
+    count per entry.  topics: list of bytes (entry 0 is the fallback topic), or the
+    (arena, off) pair commit_topic_table made."""
+    data = _dev(data, torch.uint8, "data")
+    rec_off = _dev(rec_off, torch.int64, "rec_off")
+    n = int(rec_off.numel()) - 1
+    dev = data.device
+    if data.numel() == 0:  # an empty batch still initialises last / count
+        data = torch.zeros(16, dtype=torch.uint8, device=dev)
+    arena, off = topics if isinstance(topics, tuple) else commit_topic_table(topics, dev)
+    arena = _dev(arena, torch.uint8, "topic arena")
+    off = _dev(off, torch.int32, "topic offsets")
+    if arena.numel() < COMMIT_TABLE_BYTES:
+        raise SbeError(f"the topic arena must hold {COMMIT_TABLE_BYTES} bytes")
+    k = int(off.numel()) - 1
+    if out is None:
+        m = max(n, 1)
+        out = CommitPlan(*(torch.empty(m, dtype=t, device=dev) for t in
+                           (torch.uint8, torch.uint8, torch.uint8, torch.int32, torch.int32, torch.int32)),
+                         torch.empty(max(k, 1), dtype=torch.int64, device=dev),
+                         torch.empty(max(k, 1) + 2, dtype=torch.int64, device=dev))
+    d = _Decoded(*(getattr(dec, f).data_ptr() for f in ("status", "flags", "hdr", "ts", "view_off", "view_len")))
+    o = _CommitOut(*(getattr(out, f).data_ptr() for f, _ in _COMMIT_KEYS))
+    rc = lib().sbe_classify_commits(_ptr(data), _ptr(rec_off), n, ctypes.byref(d), _ptr(arena), _ptr(off), k,
+                                    ctypes.byref(o), None, 0, _stream(stream))
+    _check(rc, "sbe_classify_commits")
+    if n < out.cm.numel():
+        out = CommitPlan(*(getattr(out, f)[:n] for f, _ in _COMMIT_KEYS[:6]), out.last, out.count)
+    return out
 
 
 @dataclass

@@ -37,6 +37,11 @@
  *                                  :833-954, decode_topic_message_with_sbe :957-1143,
  *                                  parse_session_event :618-647) → ParseResult
  *                                  include/aeron_cluster/sbe_messages.hpp:306-412
+ * sbe_classify_commits()          the commit decision of ClusterClient::handle_incoming_message
+ *                                  src/cluster_client.cpp:1198-1303: should_skip_auto_commit :847-886,
+ *                                  extract_topic_from_message :756-806, and the last commit per
+ *                                  topic that CommitManager::commit_message keeps
+ *                                  (src/commit_manager.cpp:29-35)
  * sbe_decode_batch(ON_EGRESS)     decode_ack  src/ack_decoder.cpp:29-105 (AckInfo
  *                                  include/aeron_cluster/ack_decoder.hpp:9-15) and
  *                                  MessageHandler::on_egress include/aeron_cluster/message_handler.hpp:35-68
@@ -304,6 +309,78 @@ size_t sbe_materialize_workspace_size(uint64_t n);
 int sbe_materialize_views(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
                           uint8_t* arena, uint64_t arena_capacity, uint64_t* arena_off, void* workspace,
                           size_t workspace_bytes, void* stream);
+
+/* ============================ auto-commit classification ============================ */
+/* The second half of ClusterClient::handle_incoming_message (src/cluster_client.cpp:1198-1303)
+ * for a decoded batch: should_skip_auto_commit (:847-886), extract_topic_from_message (:756-806)
+ * and the commit test (:1251), per record, after sbe_decode_batch(SBE_DEC_PARSE_MESSAGE) on the
+ * same in / rec_off (dec: its outputs).  cm[i] is the first clause that fires, in the reference's
+ * order: */
+#define SBE_CM_COMMIT 0u             /* reaches commit_message (given a successful callback: the host's business) */
+#define SBE_CM_NOT_PARSED 1u         /* status >= 16 (result.success false) */
+#define SBE_CM_SKIP_TYPE 2u          /* message_type is one of the six literals (:849-854); every SBE_ST_ACK */
+#define SBE_CM_SKIP_ACK_ID 3u        /* message_id starts with "ack_" (:859) */
+#define SBE_CM_SKIP_TOPIC 4u         /* the extracted topic is "_ack" or "_subscriptions" */
+#define SBE_CM_SKIP_CONTROL 5u       /* topic "_control", message_type not REPLAY_COMPLETE and no
+                                        "REPLAY_COMPLETE" in the payload bytes (:871-878) */
+#define SBE_CM_SKIP_EMPTY_PAYLOAD 6u /* empty payload (:881; not reached by a _control REPLAY_COMPLETE) */
+#define SBE_CM_NO_ID 7u              /* not skipped, but message_id is empty (:1251); every
+                                        SBE_ST_SESSION_EVENT (message_id is never set there, so what
+                                        should_skip_auto_commit returns cannot be observed) */
+/* where the topic came from (extract_topic_from_message); NONE: extraction did not run (the
+ * record stopped at an earlier clause, or is not a TopicMessage) */
+#define SBE_TOPIC_SRC_NONE 0u
+#define SBE_TOPIC_SRC_HEADERS 1u         /* headers.topic */
+#define SBE_TOPIC_SRC_PAYLOAD 2u         /* payload.topic */
+#define SBE_TOPIC_SRC_PAYLOAD_MESSAGE 3u /* payload.message.topic */
+#define SBE_TOPIC_SRC_FALLBACK 4u        /* the caller's topic, table entry 0 (*subscribed_topics_.begin() or "default") */
+/* what the topic token is; the host applies Value::asString to the non-string kinds */
+#define SBE_TOPIC_KIND_NONE 0u       /* no token (sources NONE and FALLBACK) */
+#define SBE_TOPIC_KIND_STRING 1u     /* no backslash: the range is the topic verbatim */
+#define SBE_TOPIC_KIND_STRING_ESC 2u /* the host decodes the escapes */
+#define SBE_TOPIC_KIND_NUMBER 3u     /* asString: decimal or "%.17g" text */
+#define SBE_TOPIC_KIND_TRUE 4u       /* "true" */
+#define SBE_TOPIC_KIND_FALSE 5u      /* "false" */
+#define SBE_TOPIC_KIND_NULL 6u       /* "" */
+#define SBE_TOPIC_UNKNOWN 0xFFFFFFFFu /* no table entry equals the topic; also every non-commit record */
+#define SBE_TOPIC_HOST 0xFFFFFFFEu    /* a non-string kind: the host converts and looks it up */
+#define SBE_COMMIT_MAX_TOPICS 64u
+#define SBE_COMMIT_TABLE_BYTES 4096u
+
+/* Outputs, device arrays.  topic_off / topic_len: the topic token relative to the record's first
+ * byte (strings: between the quotes; numbers and literals: the token), 0 for sources NONE and
+ * FALLBACK.  topic_idx: for SBE_CM_COMMIT records the first table entry equal to the decoded
+ * topic (FALLBACK: 0), SBE_TOPIC_UNKNOWN or SBE_TOPIC_HOST; SBE_TOPIC_UNKNOWN for every other
+ * record.  last [k]: the largest SBE_CM_COMMIT record index per table entry (UINT64_MAX: none).
+ * count [k + 2]: SBE_CM_COMMIT records per entry, then those with SBE_TOPIC_UNKNOWN, then those
+ * with SBE_TOPIC_HOST. */
+typedef struct sbe_commit_out {
+    uint8_t* cm;         /* [n] */
+    uint8_t* topic_src;  /* [n] */
+    uint8_t* topic_kind; /* [n] */
+    uint32_t* topic_off; /* [n] */
+    uint32_t* topic_len; /* [n] */
+    uint32_t* topic_idx; /* [n] */
+    uint64_t* last;      /* [k] */
+    uint64_t* count;     /* [k + 2] */
+} sbe_commit_out;
+
+/* Workspace bytes sbe_classify_commits needs (0: none; workspace may then be NULL). */
+size_t sbe_commit_workspace_size(uint64_t n, uint32_t k);
+
+/* Classify n decoded records.  The topic table: k entries (1..SBE_COMMIT_MAX_TOPICS), entry j =
+ * topic_arena[topic_off[j] .. topic_off[j+1]) (topic_off: device u32 [k + 1]); entry 0 is the
+ * fallback topic.  topic_arena must be readable for SBE_COMMIT_TABLE_BYTES bytes: the host does not
+ * read topic_off, the kernel clamps every offset to that size (and an entry whose end lies before
+ * its start to length 0), so it stays inside the arena whatever topic_off holds.  The call sets
+ * last and count itself on `stream` (two calls in a row give the same result); n == 0 is SBE_OK
+ * with both initialised: only out, out->last, out->count and k are checked then, the per-record
+ * arrays and the topic table are not looked at and may be null.  SBE_EINVAL (nothing written): a
+ * null pointer, k == 0 or k > SBE_COMMIT_MAX_TOPICS, a u32 array not 4-byte or a u64 array not
+ * 8-byte aligned. */
+int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                         const uint8_t* topic_arena, const uint32_t* topic_off, uint32_t k,
+                         const sbe_commit_out* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ============================ Aeron fragment reassembly ============================ */
 /* Replaces LocalFragmentReassembler::onFragment (src/cluster_client.cpp:39-82) for a batch of

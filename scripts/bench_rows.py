@@ -342,11 +342,71 @@ def row_materialize(steps, warmup):
     line("materialize", n, ms * 1e-3, {"sbe_materialize_views (all launches)": (ms, nbytes)})
 
 
+def _event_ms(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def row_autocommit(steps, warmup):
+    """sbe_classify_commits after a parse_message decode, three 1 M-record batches: fixed-256 Orders
+    (no source holds "topic" or a backslash: no record is parsed), the config-3 mix, and fixed-256
+    Orders whose headers all carry "topic" (every lane runs the JSON reader).  Bytes: views 1..4
+    read, 42 B of descriptors (rec_off 8, status 1, flags 1, four view offsets and lengths 32) and
+    15 B of outputs a record.  The fixed-256 batch also times the decode of the same
+    buffers in the same run (decode reads the same record bytes)."""
+    n = 1_000_000
+    arena, L, ts = T.fixed256_orders(n)
+    fixed = T.oracle_encode(arena, L, ts)[:2]
+    worst_arena = arena.reshape(n, 222).copy()
+    worst_arena[:, 190:] = np.frombuffer(b'{"topic":"orders","a":"CREATE"} ', np.uint8)
+    worst = T.oracle_encode(worst_arena.reshape(-1), L, ts)[:2]
+    topics = [b"orders", b"order_request_topic", b"order_notification_topic"]
+    for name, (data, off) in (("fixed256", fixed), ("config3_mixed", T.mixed_records(n)), ("all_parse", worst)):
+        d0, o0 = dev(data, torch.uint8), dev(np.asarray(off, np.uint64), torch.int64)
+        table = sbecodec.commit_topic_table(topics, "cuda")
+
+        def make(k):
+            d, o = d0.clone(), o0.clone()
+            dec = sbecodec.decode_batch(d, o, sbecodec.DEC_PARSE_MESSAGE, out=sbecodec.alloc_decoded(n, "cuda"),
+                                        in_bytes=data.size)
+            return d, o, dec, sbecodec.classify_commits(d, o, dec, table)
+        R = Rot(make)
+        torch.cuda.synchronize()
+        dec0, plan0 = R.sets[0][2], R.sets[0][3]
+        tm = dec0.status[:n] == 0
+        vbytes = int((dec0.view_len[:n, 1:].to(torch.int64).sum(dim=1) * tm).sum().item())
+        cm = np.bincount(plan0.numpy()["cm"], minlength=8).tolist()
+
+        def fn():
+            d, o, dec, plan = R.next()
+            sbecodec.classify_commits(d, o, dec, table, out=plan)
+        ms = _event_ms(fn, steps, warmup)
+        kernels = {"sbe_classify_commits (init + classify)": (ms, vbytes + (42 + 15) * n)}
+        if name == "fixed256":
+            def dfn():
+                d, o, dec, _ = R.next()
+                sbecodec.decode_batch(d, o, sbecodec.DEC_PARSE_MESSAGE, out=dec, in_bytes=data.size)
+            dms = _event_ms(dfn, steps, warmup)
+            kernels["sbe_decode_batch (same buffers, same run)"] = (dms, int(off[-1]) + 8 * n + DESC * n)
+        line(f"autocommit_{name}", n, ms * 1e-3, kernels)
+        print(json.dumps({"row": f"autocommit_{name}", "cm_counts": cm}), flush=True)
+        del R
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,materialize")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,materialize,autocommit")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -371,6 +431,8 @@ def main():
             row_order_json(args.steps, args.warmup)
         elif r == "materialize":
             row_materialize(args.steps, args.warmup)
+        elif r == "autocommit":
+            row_autocommit(args.steps, args.warmup)
         elif r.startswith("lite"):
             row_lite(int(r[4:]), args.steps, args.warmup)
         torch.cuda.empty_cache()

@@ -1,6 +1,7 @@
 """Run the encode (pack) or the parse_message decode of one workload K times with a given library
 build, for rocprofv3 PMC passes on one kernel.  Usage: python scripts/k_run.py LIB [--var] [--k K]
-[--enc]  (default: decode; --enc: encode, K times)"""
+[--enc | --commit]  (default: decode; --enc: encode; --commit: one decode, then sbe_classify_commits;
+each K times)"""
 import os
 import sys
 
@@ -29,6 +30,12 @@ if "--enc" in sys.argv:
     ws = sbecodec.alloc_workspace(n, dev)
     for _ in range(k):
         sbecodec.encode_topic_batch(a, l, t, out=enc.out, out_off=enc.out_off, status=enc.status, workspace=ws)
+elif "--commit" in sys.argv:
+    dec = sbecodec.decode_batch(enc.out, enc.out_off, out=sbecodec.alloc_decoded(n, dev))
+    table = sbecodec.commit_topic_table([b"orders", b"order_request_topic", b"order_notification_topic"], dev)
+    plan = sbecodec.classify_commits(enc.out, enc.out_off, dec, table)
+    for _ in range(k):
+        sbecodec.classify_commits(enc.out, enc.out_off, dec, table, out=plan)
 else:
     dec = sbecodec.alloc_decoded(n, dev)
     for _ in range(k):
