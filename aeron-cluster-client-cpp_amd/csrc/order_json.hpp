@@ -966,6 +966,34 @@ __global__ __launch_bounds__(kScanThreads) void order_json_scan_blocks(uint64_t*
 #ifndef SBE_OJ_HSTAGE
 #define SBE_OJ_HSTAGE 1
 #endif
+// The packed-arena staging of a sizing launch: the strings of the wave's Orders [i0, i0 + 64) are
+// one contiguous arena range [g0, end) (g0 rounded down to 16); when it fits kBytes the wave copies
+// it into its LDS share sb with coalesced 16-byte loads and returns true (sb[0] = arena[g0]).
+// base / tot: this lane's string base and string bytes.  Uniform per wave.
+template <uint32_t kBytes>
+__device__ __forceinline__ bool stage_wave_strings(const uint8_t* arena, uint8_t* sb, uint64_t base, uint64_t tot,
+                                                   uint64_t n, uint64_t i0, uint32_t lane, uint64_t& g0) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    if (i0 >= n) return false;
+    g0 = lane_u64(base, 0) & ~15ull;
+    const uint64_t last = n - 1 - i0 < kWave - 1 ? n - 1 - i0 : kWave - 1;
+    const uint64_t end = lane_u64(base + tot, (int)last);
+    if (end - g0 > kBytes) return false;
+    typedef const __attribute__((address_space(1))) u32x4 g128;
+    typedef __attribute__((address_space(3))) u32x4 l128;
+    const uint64_t nb = (end - g0 + 15) / 16;
+    for (uint64_t c = lane; c < nb; c += kWave) {
+        const uint64_t o = g0 + 16 * c;
+        if (o + 16 <= end) {
+            *(l128*)(sb + 16 * c) = *(g128*)(arena + o);
+        } else {  // the range's partial last chunk: bytewise, never past the wave's last
+                  // string byte (the arena may end there, at the end of a mapping)
+            for (uint64_t k = 0; k < end - o; ++k) sb[16 * c + k] = arena[o + k];
+        }
+    }
+    return true;
+}
+
 template <uint32_t kWhat>
 __global__ __launch_bounds__(kBlock) void order_json_measure(JsonArgs a) {
     __shared__ uint64_t wtot[kBlock / kWave];
@@ -985,32 +1013,10 @@ __global__ __launch_bounds__(kBlock) void order_json_measure(JsonArgs a) {
         const uint64_t base = a.blk_str[blockIdx.x] + block_excl_scan(tot, wtot, lane, wv, total);
         if (live) a.str_base[i] = base;
 #if SBE_OJ_MSTR > 0
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         constexpr bool kStage = kWhat != SBE_JSON_PUBLISH_HEADERS || SBE_OJ_HSTAGE;
         __shared__ __attribute__((aligned(16))) uint8_t sbuf[kBlock / kWave][kStage ? SBE_OJ_MSTR : 16];
-        const uint64_t i0 = i - lane;
-        bool staged = false;
         uint64_t g0 = 0;
-        if (kStage && i0 < a.n) {  // uniform per wave
-            g0 = lane_u64(base, 0) & ~15ull;
-            const uint64_t last = a.n - 1 - i0 < kWave - 1 ? a.n - 1 - i0 : kWave - 1;
-            const uint64_t end = lane_u64(base + tot, (int)last);
-            staged = end - g0 <= (kStage ? SBE_OJ_MSTR : 0);
-            if (staged) {
-                typedef const __attribute__((address_space(1))) u32x4 g128;
-                typedef __attribute__((address_space(3))) u32x4 l128;
-                const uint64_t nb = (end - g0 + 15) / 16;
-                for (uint64_t c = lane; c < nb; c += kWave) {
-                    const uint64_t o = g0 + 16 * c;
-                    if (o + 16 <= end) {
-                        *(l128*)(sbuf[wv] + 16 * c) = *(g128*)(a.arena + o);
-                    } else {  // the range's partial last chunk: bytewise, never past the wave's last
-                              // string byte (the arena may end there, at the end of a mapping)
-                        for (uint64_t k = 0; k < end - o; ++k) sbuf[wv][16 * c + k] = a.arena[o + k];
-                    }
-                }
-            }
-        }
+        const bool staged = kStage && stage_wave_strings<(kStage ? SBE_OJ_MSTR : 0)>(a.arena, sbuf[wv], base, tot, a.n, i - lane, lane, g0);
         __syncthreads();
         if (staged && live) {
             lr8* f[kFields];
@@ -1084,22 +1090,21 @@ __device__ inline uint64_t wave_max(uint64_t v) {
     return v;
 }
 
-// The staging and storing half of the writing launch: every live lane knows its text's output
-// range [o, e) and its fields; the wave's texts go through the LDS window `win`.
-template <uint32_t kWhat, class P>
-__device__ __forceinline__ void write_texts(const JsonArgs& a, lw8* win, uint32_t lane, uint64_t i, bool live,
-                                            uint64_t o, uint64_t e, P const f[kFields], const uint32_t l[kFields]) {
-    constexpr uint32_t kWin = WShape<kWhat>::kWinB;
-    bool done = true;
-    if (live) {
-        const bool fits = e <= a.cap;
-        if (a.status) a.status[i] = fits ? SBE_JSON_OK : SBE_JSON_OVERFLOW;
-        done = !fits;
-        if (fits && e - o > kWin - 16) {  // larger than any window: straight to HBM
-            HbmSink w((gw8*)(a.out + o));
-            order_text<kWhat>(w, a, i, f, l);
-            done = true;
-        }
+// The staging and storing half of a writing launch, shared by the text writer below and the record
+// writer of order_publish.hpp.  Every lane with todo set knows its piece's output range [o, e)
+// (e <= the output capacity) and writes exactly those bytes through emit(sink); the wave's pieces
+// are contiguous in `out` but for pieces with todo clear, which are empty or past the capacity.
+// A piece larger than the kWin-byte LDS window `win` goes from its lane straight to HBM; every
+// emitted piece is longer than 16 bytes (a text's skeleton is 58), so such a piece never shares a
+// window pass with pieces on both of its sides.
+template <uint32_t kWin, class Emit>
+__device__ __forceinline__ void write_staged(uint8_t* out, lw8* win, uint32_t lane, bool todo, uint64_t o, uint64_t e,
+                                             Emit emit) {
+    bool done = !todo;
+    if (todo && e - o > kWin - 16) {  // larger than any window: straight to HBM
+        HbmSink w((gw8*)(out + o));
+        emit(w);
+        done = true;
     }
     uint64_t start = ~0ull;  // output coordinate of the first record still to stage
     for (int d = 32; d >= 1; d >>= 1) {
@@ -1112,11 +1117,11 @@ __device__ __forceinline__ void write_texts(const JsonArgs& a, lw8* win, uint32_
         start = t < start ? t : start;
     }
     while (start != ~0ull) {  // uniform: every lane holds the same start
-        const uint64_t wbase = start - (uint64_t)((uintptr_t)(a.out + start) & 15);  // win[0] ≡ out + wbase (mod 16)
+        const uint64_t wbase = start - (uint64_t)((uintptr_t)(out + start) & 15);  // win[0] ≡ out + wbase (mod 16)
         uint64_t my_end = 0;
         if (!done && e - wbase <= kWin) {
             LdsSink w(win + (o - wbase), (uint32_t)(e - o));
-            order_text<kWhat>(w, a, i, f, l);
+            emit(w);
             done = true;
             my_end = e;
         }
@@ -1130,9 +1135,9 @@ __device__ __forceinline__ void write_texts(const JsonArgs& a, lw8* win, uint32_
                 typedef const __attribute__((address_space(3))) u32x4 lu128;
                 const u32x4 v = *(lu128*)(win + 16 * c);
                 // out + x0 is 16-byte aligned (wbase's choice): one dwordx4 store a chunk
-                __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(a.out + x0));
+                __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(out + x0));
             } else {
-                for (uint64_t x = x0 < start ? start : x0; x < x0 + 16 && x < cend; ++x) a.out[x] = win[x - wbase];
+                for (uint64_t x = x0 < start ? start : x0; x < x0 + 16 && x < cend; ++x) out[x] = win[x - wbase];
             }
         }
         __syncthreads();
@@ -1143,6 +1148,17 @@ __device__ __forceinline__ void write_texts(const JsonArgs& a, lw8* win, uint32_
         }
         start = nx;
     }
+}
+
+// Every live lane knows its text's output range [o, e) and its fields; the wave's texts go
+// through the LDS window `win`.
+template <uint32_t kWhat, class P>
+__device__ __forceinline__ void write_texts(const JsonArgs& a, lw8* win, uint32_t lane, uint64_t i, bool live,
+                                            uint64_t o, uint64_t e, P const f[kFields], const uint32_t l[kFields]) {
+    const bool fits = live && e <= a.cap;
+    if (live && a.status) a.status[i] = fits ? SBE_JSON_OK : SBE_JSON_OVERFLOW;
+    write_staged<WShape<kWhat>::kWinB>(a.out, win, lane, fits, o, e,
+                                       [&](auto& w) { order_text<kWhat>(w, a, i, f, l); });
 }
 
 #ifndef SBE_OJ_MINW  // A/B builds: minimum waves per SIMD the writing launch's registers must allow

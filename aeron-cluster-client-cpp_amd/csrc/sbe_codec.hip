@@ -4815,6 +4815,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 
 // after every other kernel, so that this file's earlier device code keeps its place in the code object
 #include "commit_class.hpp"
+#include "order_publish.hpp"
 
 }  // namespace
 
@@ -5544,6 +5545,103 @@ int sbe_order_to_json_batch(const sbe_order_batch* in, uint64_t n, uint32_t what
         hipLaunchKernelGGL(oj::order_json_write<SBE_JSON_ORDER_PAYLOAD>, dim3((uint32_t)((n + t - 1) / t)),
                            dim3(oj::kWWave), 0, s, a);
     }
+    return record_hip(hipGetLastError());
+}
+
+size_t sbe_publish_orders_workspace_size(uint64_t n) {
+    // record sizes and string bases (8 B each), the two text lengths (2 x 4 B), three block-sum
+    // arrays, alignment
+    const uint64_t nblk = (n + oj::kBlock - 1) / oj::kBlock;
+    return (size_t)(24 * n + 24 * nblk + 6 * 16);
+}
+
+uint64_t sbe_publish_orders_output_bound(uint64_t n, uint64_t string_bytes, uint32_t topic_len, int session) {
+    // fixed text (payload skeleton and numbers <= 900, headers skeleton 58), overhead, messageType
+    return n * (1024ull + topic_len + (session ? SBE_SESSION_HDR_LEN : 0u)) + 19 * string_bytes + 64;
+}
+
+int sbe_publish_orders_batch(const sbe_order_batch* orders, const sbe_order_checks* checks, uint64_t n,
+                             const uint8_t* topic, uint32_t topic_len, const uint64_t* timestamp,
+                             uint64_t ts_default, uint32_t flags, int session, int64_t leadership_term_id,
+                             int64_t cluster_session_id, uint8_t* out, uint64_t out_capacity, uint64_t* out_off,
+                             uint8_t* status, uint16_t* error_mask, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!orders || !out_off) return SBE_EINVAL;
+    if (flags & ~SBE_ENC_REF_TRUNCATE8) return SBE_EINVAL;  // SBE_ENC_PUBLISH_TOPIC included
+    if (session != 0 && session != 1) return SBE_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(out) & 15u) || (reinterpret_cast<uintptr_t>(out_off) & 7u) ||
+        (reinterpret_cast<uintptr_t>(error_mask) & 1u) || (reinterpret_cast<uintptr_t>(workspace) & 15u))
+        return SBE_EINVAL;
+    if (!out && out_capacity) return SBE_EINVAL;
+    if (!topic && topic_len) return SBE_EINVAL;
+    if (n) {
+        if (!orders->arena || !orders->str_len || !orders->customer_id || !orders->timestamp || !orders->quantity ||
+            !workspace)
+            return SBE_EINVAL;
+        if (checks && (!checks->arena || !checks->str_len || !checks->limit_price || !checks->stop_price ||
+                       !checks->present))
+            return SBE_EINVAL;
+        if ((n + pub::kPubOpw - 1) / pub::kPubOpw > 0x7fffffffull) return SBE_EINVAL;
+        if (workspace_bytes < sbe_publish_orders_workspace_size(n)) return SBE_ENOSPC;
+    }
+    if (n == 0) return record_hip(hipMemsetAsync(out_off, 0, 8, s));
+    const uint64_t nblk = (n + oj::kBlock - 1) / oj::kBlock;
+    auto al = [](uintptr_t x) { return (x + 15) & ~(uintptr_t)15; };
+    uintptr_t w = reinterpret_cast<uintptr_t>(workspace);
+    pub::PubArgs a{};
+    a.j.arena = orders->arena;
+    a.j.str_off = orders->str_off;
+    a.j.str_len = orders->str_len;
+    a.j.customer_id = orders->customer_id;
+    a.j.timestamp = orders->timestamp;
+    a.j.quantity = orders->quantity;
+    a.j.n = n;
+    a.j.out = out;
+    a.j.cap = out_capacity;
+    a.j.out_off = out_off;
+    a.j.status = status;
+    a.j.sz = reinterpret_cast<uint64_t*>(w);
+    w = al(w + 8 * n);
+    a.j.str_base = reinterpret_cast<uint64_t*>(w);
+    w = al(w + 8 * n);
+    a.tl = reinterpret_cast<uint32_t*>(w);
+    w = al(w + 8 * n);
+    a.j.blk_str = reinterpret_cast<uint64_t*>(w);
+    w = al(w + 8 * nblk);
+    a.j.blk_txt = reinterpret_cast<uint64_t*>(w);
+    w = al(w + 8 * nblk);
+    a.blk_chk = reinterpret_cast<uint64_t*>(w);
+    if (checks) {
+        a.chk_arena = checks->arena;
+        a.chk_off = checks->str_off;
+        a.chk_len = checks->str_len;
+        a.limit_price = checks->limit_price;
+        a.stop_price = checks->stop_price;
+        a.present = checks->present;
+    }
+    a.topic = topic;
+    a.topic_len = topic_len;
+    a.tm_ts = timestamp;
+    a.ts_default = ts_default;
+    a.cut = (flags & SBE_ENC_REF_TRUNCATE8) ? SBE_TM_WIRE_OVERHEAD - SBE_TM_REF_OVERHEAD : 0u;
+    a.session = (uint32_t)session;
+    a.term = leadership_term_id;
+    a.sess = cluster_session_id;
+    a.mask = error_mask;
+    const uint32_t blocks = (uint32_t)nblk;
+    const bool chk_packed = checks && !checks->str_off;
+    if (!orders->str_off || chk_packed) {
+        hipLaunchKernelGGL(pub::publish_totals, dim3(blocks), dim3(oj::kBlock), 0, s, a);
+        if (!orders->str_off)
+            hipLaunchKernelGGL(oj::order_json_scan_blocks, dim3(1), dim3(oj::kScanThreads), 0, s, a.j.blk_str, nblk);
+        if (chk_packed)
+            hipLaunchKernelGGL(oj::order_json_scan_blocks, dim3(1), dim3(oj::kScanThreads), 0, s, a.blk_chk, nblk);
+    }
+    hipLaunchKernelGGL(pub::publish_measure, dim3(blocks), dim3(oj::kBlock), 0, s, a);
+    hipLaunchKernelGGL(oj::order_json_scan_blocks, dim3(1), dim3(oj::kScanThreads), 0, s, a.j.blk_txt, nblk);
+    hipLaunchKernelGGL(pub::publish_write, dim3((uint32_t)((n + pub::kPubOpw - 1) / pub::kPubOpw)),
+                       dim3(oj::kWWave), 0, s, a);
     return record_hip(hipGetLastError());
 }
 

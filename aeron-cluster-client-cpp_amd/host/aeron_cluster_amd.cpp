@@ -25,6 +25,7 @@
 #include <iostream>
 #include <map>
 #include <mutex>
+#include <random>
 #include <sstream>
 #include <stdexcept>
 #include <thread>
@@ -2029,6 +2030,223 @@ OrderJsonBatch orders_to_json(const std::vector<Order>& orders, const std::vecto
 std::string Order::to_json() const {
     OrderJsonBatch b = orders_to_json({*this}, {std::string()});
     return std::string(b.payload.bytes.begin(), b.payload.bytes.end());
+}
+
+// ---- Order::validate and the fused publish path ----
+namespace {
+const char* const kValidateText[SBE_PUB_INVALID_COUNT] = {
+    "Order ID is required",
+    "Base token is required",
+    "Quote token is required",
+    "Side must be 'BUY' or 'SELL'",
+    "Quantity must be positive",
+    "Invalid order type: ",
+    "Limit price must be positive for LIMIT orders",
+    "Stop price must be positive for STOP orders",
+    "Stop price must be positive for STOP_LIMIT orders",
+    "Limit price must be positive for STOP_LIMIT orders",
+    "Invalid time in force: ",
+    "Expiry timestamp required for GTD orders"};
+
+std::string default_message_id() {  // src/order_types.cpp:428-437
+    const int64_t ts = std::chrono::high_resolution_clock::now().time_since_epoch().count();
+    thread_local std::mt19937 gen{std::random_device{}()};
+    std::uniform_int_distribution<uint32_t> dis(10000, 99999);
+    return "msg_" + std::to_string(ts) + "_" + std::to_string(dis(gen));
+}
+}  // namespace
+
+std::vector<std::string> Order::validate() const {
+    std::vector<std::string> errors;
+    if (id.empty()) errors.push_back("Order ID is required");
+    if (base_token.empty()) errors.push_back("Base token is required");
+    if (quote_token.empty()) errors.push_back("Quote token is required");
+    if (!(side == "BUY" || side == "SELL")) errors.push_back("Side must be 'BUY' or 'SELL'");
+    if (quantity <= 0.0) errors.push_back("Quantity must be positive");
+    if (!(order_type == "MARKET" || order_type == "LIMIT" || order_type == "STOP" || order_type == "STOP_LIMIT"))
+        errors.push_back("Invalid order type: " + order_type);
+    if (order_type == "LIMIT" && limit_price <= 0.0) errors.push_back("Limit price must be positive for LIMIT orders");
+    if (order_type == "STOP" && (!stop_price.has_value() || stop_price.value() <= 0.0))
+        errors.push_back("Stop price must be positive for STOP orders");
+    if (order_type == "STOP_LIMIT") {
+        if (!stop_price.has_value() || stop_price.value() <= 0.0)
+            errors.push_back("Stop price must be positive for STOP_LIMIT orders");
+        if (limit_price <= 0.0) errors.push_back("Limit price must be positive for STOP_LIMIT orders");
+    }
+    if (!(time_in_force == "GTC" || time_in_force == "IOC" || time_in_force == "FOK" || time_in_force == "DAY" ||
+          time_in_force == "GTD"))
+        errors.push_back("Invalid time in force: " + time_in_force);
+    if (time_in_force == "GTD" && !expiry_timestamp.has_value())
+        errors.push_back("Expiry timestamp required for GTD orders");
+    return errors;
+}
+
+OrderPublisher::OrderPublisher(OfferFn offer, std::string default_topic, OrderPublisherOptions options)
+    : offer_(std::move(offer)), default_topic_(std::move(default_topic)), opt_(std::move(options)) {
+    if (!opt_.message_id) opt_.message_id = default_message_id;
+    if (!opt_.clock)
+        opt_.clock = [] { return (uint64_t)std::chrono::high_resolution_clock::now().time_since_epoch().count(); };
+}
+
+std::string OrderPublisher::validation_message(unsigned k, const Order& order) {
+    if (k >= SBE_PUB_INVALID_COUNT) return std::string();
+    std::string m = kValidateText[k];
+    if (k == SBE_PUB_INVALID_ORDER_TYPE - SBE_PUB_INVALID_ID) m += order.order_type;
+    if (k == SBE_PUB_INVALID_TIME_IN_FORCE - SBE_PUB_INVALID_ID) m += order.time_in_force;
+    return m;
+}
+
+PublishedOrders OrderPublisher::publish_orders_batch(const std::vector<Order>& orders) {
+    return publish_orders_batch_to_topic(orders, default_topic_);
+}
+
+PublishedOrders OrderPublisher::publish_orders_batch_to_topic(const std::vector<Order>& orders,
+                                                              const std::string& topic) {
+    const size_t n = orders.size();
+    PublishedOrders r;
+    r.message_ids.resize(n);
+    r.status.assign(n, 0);
+    r.error_mask.assign(n, 0);
+    if (n == 0) return r;
+    std::vector<uint64_t> tm_ts(n);
+    for (size_t i = 0; i < n; ++i) {  // in order: injected generators may count
+        r.message_ids[i] = opt_.message_id();
+        tm_ts[i] = opt_.clock();
+    }
+    auto field = [&](size_t i, int k) -> std::string_view {
+        const Order& o = orders[i];
+        switch (k) {
+            case 0: return o.client_order_uuid;
+            case 1: return o.identifier;
+            case 2: return o.base_token;
+            case 3: return o.quote_token;
+            case 4: return o.side;
+            case 5: return o.id;
+            case 6: return r.message_ids[i];
+            default: return o.status;
+        }
+    };
+    Ctx& c = ctx();
+    Pipeline::Slot& s = c.pipe.slot[0];  // serial use of the pipeline's first slot (idle between calls)
+    hipStream_t stream = c.batch_stream();
+    std::vector<uint64_t> pin, cpin;
+    prefix(n, pin, [&](size_t i) {
+        uint64_t t = 0;
+        for (int k = 0; k < (int)SBE_ORDER_FIELDS; ++k) t += field(i, k).size();
+        return t;
+    });
+    prefix(n, cpin, [&](size_t i) { return (uint64_t)(orders[i].order_type.size() + orders[i].time_in_force.size()); });
+    // staging layout: order arena | order lengths | customer_id, timestamp, quantity, limit, stop,
+    // TopicMessage timestamps (8 B each) | checks lengths | present | checks arena | topic
+    const size_t arena = (size_t)pin[n], carena = (size_t)cpin[n];
+    const size_t o_len = al16(arena), o_num = o_len + al16(n * 4 * SBE_ORDER_FIELDS), o_clen = o_num + n * 48,
+                 o_pres = o_clen + al16(n * 8), o_car = o_pres + al16(n), o_topic = o_car + al16(carena),
+                 stage = o_topic + al16(topic.size());
+    s.pin.need(stage);
+    uint8_t* ap = s.pin.b();
+    uint32_t* lp = reinterpret_cast<uint32_t*>(ap + o_len);
+    int64_t* cid = reinterpret_cast<int64_t*>(ap + o_num);
+    int64_t* ts = cid + n;
+    double* q = reinterpret_cast<double*>(ts + n);
+    double* lim = q + n;
+    double* stop = lim + n;
+    uint64_t* tts = reinterpret_cast<uint64_t*>(stop + n);
+    uint32_t* clp = reinterpret_cast<uint32_t*>(ap + o_clen);
+    uint8_t* pres = ap + o_pres;
+    for_ranges(n, 2048, [&](size_t x, size_t y) {
+        for (size_t i = x; i < y; ++i) {
+            const Order& o = orders[i];
+            uint8_t* at = ap + pin[i];
+            for (int k = 0; k < (int)SBE_ORDER_FIELDS; ++k) {
+                const std::string_view f = field(i, k);
+                if (!f.empty()) std::memcpy(at, f.data(), f.size());
+                at += f.size();
+                lp[SBE_ORDER_FIELDS * i + k] = (uint32_t)f.size();
+            }
+            cid[i] = o.customer_id;
+            ts[i] = o.timestamp;
+            q[i] = o.quantity;
+            lim[i] = o.limit_price;
+            stop[i] = o.stop_price.value_or(0.0);
+            tts[i] = tm_ts[i];
+            pres[i] = (uint8_t)((o.stop_price.has_value() ? SBE_PUB_HAS_STOP_PRICE : 0u) |
+                                (o.expiry_timestamp.has_value() ? SBE_PUB_HAS_EXPIRY : 0u));
+            uint8_t* cat = ap + o_car + cpin[i];
+            if (!o.order_type.empty()) std::memcpy(cat, o.order_type.data(), o.order_type.size());
+            if (!o.time_in_force.empty())
+                std::memcpy(cat + o.order_type.size(), o.time_in_force.data(), o.time_in_force.size());
+            clp[2 * i] = (uint32_t)o.order_type.size();
+            clp[2 * i + 1] = (uint32_t)o.time_in_force.size();
+        }
+    });
+    if (!topic.empty()) std::memcpy(ap + o_topic, topic.data(), topic.size());
+    s.d_in.need(stage);
+    hip_check(hipMemcpyAsync(s.d_in.p, ap, stage, hipMemcpyHostToDevice, stream), "H2D");
+    const uint8_t* di = s.d_in.b();
+    const int64_t* d_cid = reinterpret_cast<const int64_t*>(di + o_num);
+    const double* d_q = reinterpret_cast<const double*>(d_cid + 2 * n);
+    sbe_order_batch in{di, nullptr, reinterpret_cast<const uint32_t*>(di + o_len), d_cid, d_cid + n, d_q};
+    sbe_order_checks chk{di + o_car, nullptr, reinterpret_cast<const uint32_t*>(di + o_clen), d_q + n, d_q + 2 * n,
+                         di + o_pres};
+    const uint64_t* d_tts = reinterpret_cast<const uint64_t*>(d_q + 3 * n);
+    const size_t o_st = al16((n + 1) * 8), o_mask = o_st + al16(n), o_ws = o_mask + al16(2 * n);
+    const size_t wsb = sbe_publish_orders_workspace_size(n);
+    c.d_aux.need(o_ws + wsb);
+    uint64_t* d_off = reinterpret_cast<uint64_t*>(c.d_aux.b());
+    uint8_t* d_st = c.d_aux.b() + o_st;
+    uint16_t* d_mask = reinterpret_cast<uint16_t*>(c.d_aux.b() + o_mask);
+    std::vector<uint64_t> off(n + 1);
+    // a typical framed record is ~760 B; out_off always holds the full layout, so a short guess is
+    // redone once at the measured size
+    uint64_t cap = (1024 + (uint64_t)topic.size()) * n + 2 * (uint64_t)arena + 64;
+    for (int attempt = 0;; ++attempt) {
+        s.d_out.need(cap);
+        if (sbe_publish_orders_batch(&in, &chk, n, topic.empty() ? nullptr : di + o_topic, (uint32_t)topic.size(), d_tts,
+                                     0, opt_.reference_truncate8 ? SBE_ENC_REF_TRUNCATE8 : 0u,
+                                     opt_.session_framed ? 1 : 0, opt_.leadership_term_id, opt_.cluster_session_id,
+                                     s.d_out.b(), cap, d_off, d_st, d_mask, c.d_aux.b() + o_ws, wsb, stream) != SBE_OK)
+            fail("sbe_publish_orders_batch");
+        hip_check(hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, stream), "D2H");
+        hip_check(hipStreamSynchronize(stream), "sync");
+        if (off[n] <= cap || attempt > 0) break;
+        cap = off[n];
+    }
+    hip_check(hipMemcpyAsync(r.status.data(), d_st, n, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipMemcpyAsync(r.error_mask.data(), d_mask, 2 * n, hipMemcpyDeviceToHost, stream), "D2H");
+    std::vector<uint8_t> bytes((size_t)off[n]);
+    if (off[n]) hip_check(hipMemcpyAsync(bytes.data(), s.d_out.p, off[n], hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    for (size_t i = 0; i < n; ++i) {
+        if (r.status[i] != SBE_ENC_OK) continue;
+        if (!offer_(bytes.data() + off[i], (size_t)(off[i + 1] - off[i]))) break;
+        ++r.offered;
+    }
+    return r;
+}
+
+namespace {
+std::string publish_one(OrderPublisher& p, const Order& order, const std::string& topic) {
+    // validate() on the host first, as the reference does (src/cluster_client.cpp:303-306): an
+    // invalid order makes no message id, reads no clock and costs no device call
+    const std::vector<std::string> errors = order.validate();
+    if (!errors.empty()) throw InvalidMessageException("Order validation failed: " + errors[0]);
+    const PublishedOrders r = p.publish_orders_batch_to_topic({order}, topic);
+    const uint8_t st = r.status[0];
+    if (st >= SBE_PUB_INVALID_ID && st < SBE_PUB_INVALID_ID + SBE_PUB_INVALID_COUNT)  // the device's verdict is the same
+        throw InvalidMessageException("Order validation failed: " +
+                                      OrderPublisher::validation_message(st - SBE_PUB_INVALID_ID, order));
+    // E109 makes create_topic_message throw, publish_message return false (src/session_manager.cpp:1111-1114);
+    // a refused offer does the same: the reference's base message (src/cluster_client.cpp:325-329)
+    if (st != SBE_ENC_OK || r.offered != 1) throw ClusterClientException("Failed to publish order message");
+    return r.message_ids[0];
+}
+}  // namespace
+
+std::string OrderPublisher::publish_order(const Order& order) { return publish_one(*this, order, default_topic_); }
+
+std::string OrderPublisher::publish_order_to_topic(const Order& order, const std::string& topic) {
+    if (topic.empty()) throw InvalidMessageException("Topic is empty");  // src/cluster_client.cpp:338-340
+    return publish_one(*this, order, topic);
 }
 
 // ======================================================================================

@@ -42,6 +42,7 @@
 #include <memory>
 #include <mutex>
 #include <optional>
+#include <stdexcept>
 #include <string>
 #include <string_view>
 #include <unordered_map>
@@ -554,8 +555,8 @@ private:
     std::vector<std::uint8_t> acc_;
 };
 
-// include/aeron_cluster/order_types.hpp:16-66: the members Order::to_json and publish_order read
-// (the reference class carries more; they play no part in the text).
+// include/aeron_cluster/order_types.hpp:16-66: the members Order::to_json, Order::validate and
+// publish_order read (the reference class carries more; they play no part in either).
 struct Order {
     std::string id;
     std::string client_order_uuid;
@@ -567,8 +568,17 @@ struct Order {
     std::string status = "CREATED";
     std::int64_t timestamp = 0;
     std::string identifier;
+    // read by validate() only (defaults: order_types.hpp:28-49)
+    std::string order_type = "LIMIT";
+    std::string time_in_force = "GTC";
+    double limit_price = 0.0;
+    std::optional<double> stop_price;
+    std::optional<std::int64_t> expiry_timestamp;
     // src/order_types.cpp:122-181 (one-record batch on the GPU)
     std::string to_json() const;
+    // src/order_types.cpp:66-120: every failed check's message, in the reference's order (host code,
+    // as in the reference; the batch publisher runs the same checks on the device)
+    std::vector<std::string> validate() const;
 };
 
 // A batch of Orders → Order::to_json texts (payload) and the headers JSON publish_order builds
@@ -579,6 +589,59 @@ struct OrderJsonBatch {
     EncodedBatch headers;
 };
 OrderJsonBatch orders_to_json(const std::vector<Order>& orders, const std::vector<std::string>& message_ids);
+
+// include/aeron_cluster/cluster_client.hpp:30-52
+class ClusterClientException : public std::runtime_error {
+public:
+    explicit ClusterClientException(const std::string& message) : std::runtime_error(message) {}
+};
+class InvalidMessageException : public ClusterClientException {
+public:
+    explicit InvalidMessageException(const std::string& message)
+        : ClusterClientException("Invalid message: " + message) {}
+};
+
+// ClusterClient::publish_order / publish_order_to_topic (src/cluster_client.cpp:300-372) minus the
+// connection checks: validate, message id, messageType, both JSON texts, create_topic_message and
+// the session frame (src/session_manager.cpp:1050-1144), the record handed to an
+// offer_ingress-shaped sink.  Every form is one fused device call (sbe_publish_orders_batch).
+struct OrderPublisherOptions {
+    bool session_framed = true;        // the 32-B SessionMessageHeader first, as the live path sends
+    bool reference_truncate8 = true;   // SBE_ENC_REF_TRUNCATE8: the 26+Σlen bytes create_topic_message returns
+    std::int64_t leadership_term_id = 0;
+    std::int64_t cluster_session_id = 0;
+    // OrderUtils::generate_message_id("msg") (src/order_types.cpp:428-437): msg_<ns>_<10000..99999>
+    std::function<std::string()> message_id;
+    // the TopicMessage timestamp (high_resolution_clock nanoseconds, src/session_manager.cpp:1050-1115)
+    std::function<std::uint64_t()> clock;
+};
+struct PublishedOrders {
+    std::vector<std::string> message_ids;  // one per order, made whether or not the order is valid
+    std::vector<std::uint8_t> status;      // SBE_ENC_OK, SBE_ENC_E109_*, SBE_PUB_INVALID_* (first message)
+    std::vector<std::uint16_t> error_mask; // bit k: validate()'s message k
+    std::size_t offered = 0;               // records the sink accepted (stops at the first refusal)
+};
+class OrderPublisher {
+public:
+    OrderPublisher(OfferFn offer, std::string default_topic, OrderPublisherOptions options = {});
+    // Return the message id.  Throw InvalidMessageException("Order validation failed: " + errors[0])
+    // (the _to_topic form: "Topic is empty" first) and ClusterClientException("Failed to publish
+    // order message") when the sink refuses the record.  validate() runs on the host first, as in
+    // the reference: an invalid order makes no message id, reads no clock and makes no device call.
+    std::string publish_order(const Order& order);
+    std::string publish_order_to_topic(const Order& order, const std::string& topic);
+    // One device call for all orders; the valid records are offered in order.  Does not throw on an
+    // invalid order or a refused offer: see status / offered.
+    PublishedOrders publish_orders_batch(const std::vector<Order>& orders);
+    PublishedOrders publish_orders_batch_to_topic(const std::vector<Order>& orders, const std::string& topic);
+    // The message text of validate()'s message k for this order (k < SBE_PUB_INVALID_COUNT).
+    static std::string validation_message(unsigned k, const Order& order);
+
+private:
+    OfferFn offer_;
+    std::string default_topic_;
+    OrderPublisherOptions opt_;
+};
 
 // Feeds every encoded record of a batch to an offer_ingress-shaped sink in order; returns the
 // number accepted before the first refusal.

@@ -19,6 +19,9 @@ Reference surface mirrored (paths relative to the reference tree):
                         src/ack_decoder.cpp:29-105, include/aeron_cluster/message_handler.hpp:35-68
   order_to_json_batch ~ Order::to_json src/order_types.cpp:122-181 and publish_order's headers JSON
                         src/cluster_client.cpp:308-323
+  publish_orders_batch~ ClusterClient::publish_order / publish_order_to_topic src/cluster_client.cpp:300-372
+                        (Order::validate src/order_types.cpp:66-120, both JSON texts, the TopicMessage and
+                        its session frame src/session_manager.cpp:1050-1144) in one fused call
 """
 from __future__ import annotations
 
@@ -46,6 +49,19 @@ FRAG_BEGIN, FRAG_END = 0x80, 0x40
 ORDER_FIELDS = 8  # client_order_uuid, identifier, base_token, quote_token, side, id, message_id, status
 JSON_ORDER_PAYLOAD, JSON_PUBLISH_HEADERS = 0, 1
 JSON_OK, JSON_OVERFLOW = 0, 6
+# publish_orders_batch: status 16 + k and error_mask bit k = validate()'s message k (order_types.cpp:69-117)
+PUB_INVALID_ID, PUB_INVALID_BASE_TOKEN, PUB_INVALID_QUOTE_TOKEN, PUB_INVALID_SIDE = 16, 17, 18, 19
+PUB_INVALID_QUANTITY, PUB_INVALID_ORDER_TYPE, PUB_INVALID_LIMIT_PRICE, PUB_INVALID_STOP_PRICE = 20, 21, 22, 23
+PUB_INVALID_STOP_LIMIT_STOP, PUB_INVALID_STOP_LIMIT_LIMIT = 24, 25
+PUB_INVALID_TIME_IN_FORCE, PUB_INVALID_GTD_EXPIRY = 26, 27
+PUB_INVALID_COUNT = 12
+PUB_HAS_STOP_PRICE, PUB_HAS_EXPIRY = 1, 2
+PUB_INVALID_MESSAGES = (
+    "Order ID is required", "Base token is required", "Quote token is required", "Side must be 'BUY' or 'SELL'",
+    "Quantity must be positive", "Invalid order type: ", "Limit price must be positive for LIMIT orders",
+    "Stop price must be positive for STOP orders", "Stop price must be positive for STOP_LIMIT orders",
+    "Limit price must be positive for STOP_LIMIT orders", "Invalid time in force: ",
+    "Expiry timestamp required for GTD orders")
 
 ST_TM, ST_ACK, ST_SESSION_EVENT = 0, 1, 2
 ST_ERR_NULL_EMPTY, ST_ERR_HEADER, ST_ERR_UNKNOWN_TYPE = 16, 17, 18
@@ -76,6 +92,11 @@ class _LiteBatch(ctypes.Structure):
 class _OrderBatch(ctypes.Structure):
     _fields_ = [("arena", ctypes.c_void_p), ("str_off", ctypes.c_void_p), ("str_len", ctypes.c_void_p),
                 ("customer_id", ctypes.c_void_p), ("timestamp", ctypes.c_void_p), ("quantity", ctypes.c_void_p)]
+
+
+class _OrderChecks(ctypes.Structure):
+    _fields_ = [("arena", ctypes.c_void_p), ("str_off", ctypes.c_void_p), ("str_len", ctypes.c_void_p),
+                ("limit_price", ctypes.c_void_p), ("stop_price", ctypes.c_void_p), ("present", ctypes.c_void_p)]
 
 
 class _Decoded(ctypes.Structure):
@@ -162,6 +183,16 @@ def _load():
                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.sbe_order_to_json_batch.restype = ctypes.c_int
+    lib.sbe_publish_orders_workspace_size.argtypes = [ctypes.c_uint64]
+    lib.sbe_publish_orders_workspace_size.restype = ctypes.c_size_t
+    lib.sbe_publish_orders_output_bound.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int]
+    lib.sbe_publish_orders_output_bound.restype = ctypes.c_uint64
+    lib.sbe_publish_orders_batch.argtypes = [
+        ctypes.POINTER(_OrderBatch), ctypes.POINTER(_OrderChecks), ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_size_t, ctypes.c_void_p]
+    lib.sbe_publish_orders_batch.restype = ctypes.c_int
     lib.sbe_profile_enable.argtypes = [ctypes.c_int]
     lib.sbe_profile_read.restype = ctypes.c_int
     lib.sbe_profile_read.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_int]
@@ -712,6 +743,129 @@ def order_to_json_batch(arena, str_len, customer_id, timestamp, quantity, what=J
             out = torch.empty(total, dtype=torch.uint8, device=dev)
             run(out, total)
     return OrderJson(out, out_off, status)
+
+
+# ---------------------------------------------------------------------------------------------
+# publish_order for a batch: Orders straight to wire records (sbe_publish_orders_batch)
+# ---------------------------------------------------------------------------------------------
+# bytes per Order of the default output bound: a typical framed record is ~760 B; a short guess
+# is regrown from out_off[n]
+PUBLISH_ORDER_BOUND = 1024
+
+
+@dataclass
+class PublishedOrders:
+    out: torch.Tensor         # u8 records, record i = out[out_off[i]:out_off[i+1]] (0 bytes when status != 0)
+    out_off: torch.Tensor     # i64 [n+1]
+    status: torch.Tensor      # u8 [n]: 0, ENC_E109_* (1..5), ENC_OVERFLOW, PUB_INVALID_* (16..27)
+    error_mask: torch.Tensor  # i16 [n]: bit k = validate()'s message k (all of them)
+
+
+def publish_orders_workspace_size(n: int) -> int:
+    return int(lib().sbe_publish_orders_workspace_size(n))
+
+
+def publish_orders_output_bound(n: int, string_bytes: int, topic_len: int, session: bool = True) -> int:
+    return int(lib().sbe_publish_orders_output_bound(n, string_bytes, topic_len, 1 if session else 0))
+
+
+def publish_orders_batch(arena, str_len, customer_id, timestamp, quantity, topic, checks=None, str_off=None,
+                         tm_timestamp=None, ts_default=0, flags=ENC_REF_TRUNCATE8, session=True,
+                         leadership_term_id=0, cluster_session_id=0, out=None, out_capacity=None, out_off=None,
+                         status=None, error_mask=None, workspace=None, stream=None) -> PublishedOrders:
+    """ClusterClient::publish_order for n Orders in one fused device call: validate, both JSON
+    texts, the TopicMessage and (session) its SessionMessageHeader; nothing but the records is
+    written.  The Order arrays are order_to_json_batch's; `topic` is a uint8 device tensor.
+    checks: None (no validation) or a tuple (arena uint8, str_len int32 [n,2] order_type /
+    time_in_force, limit_price f64 [n], stop_price f64 [n], present uint8 [n] (PUB_HAS_* bits)
+    [, str_off int32 [n,2]]).  tm_timestamp: int64 [n] TopicMessage timestamps (0 or None:
+    ts_default).  flags: ENC_REF_TRUNCATE8 (the live path, default) or 0 (wire-correct).
+    Self-sizes like order_to_json_batch: asynchronous when `out` or `out_capacity` is given, else
+    one synchronisation of `stream` to read out_off[n] and a rerun when the guess was short."""
+    arena = _dev(arena, torch.uint8, "arena")
+    str_len = _dev(str_len, torch.int32, "str_len")
+    customer_id = _dev(customer_id, torch.int64, "customer_id")
+    timestamp = _dev(timestamp, torch.int64, "timestamp")
+    quantity = _dev(quantity, torch.float64, "quantity")
+    topic = _dev(topic, torch.uint8, "topic")
+    if topic is None:
+        raise SbeError("topic: expected a uint8 device tensor")
+    n = int(customer_id.numel())
+    if str_len.numel() != ORDER_FIELDS * n or timestamp.numel() != n or quantity.numel() != n:
+        raise SbeError("order batch arrays disagree on n")
+    if str_off is not None:
+        str_off = _dev(str_off, torch.int32, "str_off")
+        if str_off.numel() != ORDER_FIELDS * n:
+            raise SbeError("str_off must be [n][8]")
+    if flags & ~ENC_REF_TRUNCATE8:
+        raise SbeError("publish_orders_batch takes flags 0 or ENC_REF_TRUNCATE8")
+    if tm_timestamp is not None:
+        tm_timestamp = _dev(tm_timestamp, torch.int64, "tm_timestamp")
+        if tm_timestamp.numel() != n:
+            raise SbeError("tm_timestamp must be [n]")
+    c = None
+    if checks is not None:
+        if len(checks) not in (5, 6):
+            raise SbeError("checks: (arena, str_len, limit_price, stop_price, present[, str_off])")
+        c_arena = _dev(checks[0], torch.uint8, "checks arena")
+        c_len = _dev(checks[1], torch.int32, "checks str_len")
+        c_lim = _dev(checks[2], torch.float64, "checks limit_price")
+        c_stop = _dev(checks[3], torch.float64, "checks stop_price")
+        c_pres = _dev(checks[4], torch.uint8, "checks present")
+        c_off = _dev(checks[5], torch.int32, "checks str_off") if len(checks) == 6 else None
+        if None in (c_arena, c_len, c_lim, c_stop, c_pres):
+            raise SbeError("checks: every member but str_off is required")
+        if c_len.numel() != 2 * n or c_lim.numel() != n or c_stop.numel() != n or c_pres.numel() != n or \
+                (c_off is not None and c_off.numel() != 2 * n):
+            raise SbeError("checks arrays disagree on n")
+        c = _OrderChecks(_ptr(c_arena), _ptr(c_off), _ptr(c_len), _ptr(c_lim), _ptr(c_stop), _ptr(c_pres))
+    dev = arena.device
+    grow = out is None and out_capacity is None
+    if out is None:
+        cap = out_capacity if out_capacity is not None else (PUBLISH_ORDER_BOUND + int(topic.numel())) * n + 64
+        out = torch.empty(max(int(cap), 16), dtype=torch.uint8, device=dev)
+    cap = int(out.numel()) if out_capacity is None else int(out_capacity)
+    if cap > out.numel():
+        raise SbeError(f"out_capacity {cap} exceeds the out tensor ({out.numel()} bytes)")
+    if out.data_ptr() % 16:
+        raise SbeError("out must be 16-byte aligned")
+    if out_off is None:
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if status is None:
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    if error_mask is None:
+        error_mask = torch.empty(max(n, 1), dtype=torch.int16, device=dev)  # the sizing launch writes all n
+    out = _dev(out, torch.uint8, "out")
+    out_off = _dev(out_off, torch.int64, "out_off")
+    status = _dev(status, torch.uint8, "status")
+    error_mask = _dev(error_mask, torch.int16, "error_mask")
+    if out_off.numel() < n + 1 or status.numel() < n or error_mask.numel() < n:
+        raise SbeError("out_off / status / error_mask are shorter than the batch")
+    need = publish_orders_workspace_size(n)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    b = _OrderBatch(_ptr(arena), _ptr(str_off) if str_off is not None else None, _ptr(str_len),
+                    _ptr(customer_id), _ptr(timestamp), _ptr(quantity))
+
+    def run(o, cp):
+        rc = lib().sbe_publish_orders_batch(ctypes.byref(b), ctypes.byref(c) if c is not None else None, n,
+                                            _ptr(topic) if topic.numel() else None, int(topic.numel()),
+                                            _ptr(tm_timestamp) if tm_timestamp is not None else None,
+                                            int(ts_default), int(flags), 1 if session else 0,
+                                            int(leadership_term_id), int(cluster_session_id), _ptr(o), cp,
+                                            _ptr(out_off), _ptr(status), _ptr(error_mask), _ptr(workspace),
+                                            workspace.numel(), _stream(stream))
+        _check(rc, "sbe_publish_orders_batch")
+
+    run(out, cap)
+    if grow and n:  # out_off always holds the full layout: one rerun at the measured size
+        s = stream if stream is not None else torch.cuda.current_stream()
+        s.synchronize()  # the launches ran on `stream`, which need not be torch's current stream
+        total = int(out_off[n].item())
+        if total > cap:
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+            run(out, total)
+    return PublishedOrders(out, out_off, status, error_mask)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -48,6 +48,12 @@
  * sbe_order_to_json_batch()       Order::to_json src/order_types.cpp:122-181 and publish_order's
  *                                  headers JSON src/cluster_client.cpp:308-323 (the strings that
  *                                  become the TopicMessage payload / headers)
+ * sbe_publish_orders_batch()      ClusterClient::publish_order / publish_order_to_topic
+ *                                  src/cluster_client.cpp:300-372 in one call: Order::validate
+ *                                  src/order_types.cpp:66-120, the messageType choice, both JSON texts,
+ *                                  create_topic_message and the session frame
+ *                                  src/session_manager.cpp:1050-1144 (sbe_publish_orders_workspace_size,
+ *                                  sbe_publish_orders_output_bound size its buffers)
  * sbe_serve_*()                   the same encoders / decoders for small batches (one record per
  *                                  call, as the reference's per-message API is used: parse_message per
  *                                  fragment src/cluster_client.cpp:1185, publish_topic per message)
@@ -443,6 +449,87 @@ size_t sbe_order_json_workspace_size(uint64_t n);
 int sbe_order_to_json_batch(const sbe_order_batch* in, uint64_t n, uint32_t what, uint8_t* out,
                             uint64_t out_capacity, uint64_t* out_off, uint8_t* status, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* ==================== publish_order: Orders straight to wire records ==================== */
+/* ClusterClient::publish_order (src/cluster_client.cpp:300-333) and publish_order_to_topic
+ * (:335-372) for a batch of Orders in one call.  Record i is what the reference offers for
+ * order i: [the 32-B SessionMessageHeader {24,1,111,8, termId, sessionId, 0} when `session`]
+ * the TopicMessage header {16,1,1,1}, the 16-B block (timestamp[i], 0 -> ts_default; sequence 0)
+ * and the five u16-length-prefixed fields
+ *   topic        one per call (device bytes),
+ *   messageType  "UPDATE_ORDER" when status is "UPDATED" or "CANCELLED", else "CREATE_ORDER",
+ *   uuid         the Order's message_id (field 6, made by the caller),
+ *   payload      the Order::to_json text,
+ *   headers      the {"messageId","messageType","orderId"} text,
+ * byte for byte what sbe_order_to_json_batch (twice) followed by sbe_encode_topic_batch /
+ * sbe_encode_session_batch produce, without the texts ever being written to memory on their own.
+ * flags: 0 = the wire-correct 34 + Σlen bytes; SBE_ENC_REF_TRUNCATE8 = the 26 + Σlen bytes
+ * create_topic_message returns (src/session_manager.cpp:1050-1115; the live path);
+ * SBE_ENC_PUBLISH_TOPIC is refused (SBE_EINVAL): it is not publish_order's path.
+ *
+ * Per-record status, first match wins (a failing record emits 0 bytes, the batch goes on):
+ *   SBE_PUB_INVALID_*   Order::validate() (src/order_types.cpp:66-120) ran first and its first
+ *                       message is this one ("Order validation failed: " + errors[0]); only when
+ *                       `checks` is given.  error_mask[i] (optional) has bit k set for every
+ *                       message SBE_PUB_INVALID_ID + k validate() returns.
+ *   SBE_ENC_E109_*      computeLength's order on the text lengths: topic, uuid (message_id),
+ *                       payload text, headers text longer than 65534 bytes.
+ *   SBE_ENC_OVERFLOW    the record ends past out_capacity (nothing is written past it).
+ * Comparisons are the reference's: strings match exactly; `quantity <= 0.0` is false for NaN (a
+ * NaN quantity passes) and true for -0.0. */
+#define SBE_PUB_INVALID_ID 16u               /* "Order ID is required" */
+#define SBE_PUB_INVALID_BASE_TOKEN 17u       /* "Base token is required" */
+#define SBE_PUB_INVALID_QUOTE_TOKEN 18u      /* "Quote token is required" */
+#define SBE_PUB_INVALID_SIDE 19u             /* "Side must be 'BUY' or 'SELL'" */
+#define SBE_PUB_INVALID_QUANTITY 20u         /* "Quantity must be positive" */
+#define SBE_PUB_INVALID_ORDER_TYPE 21u       /* "Invalid order type: " + order_type */
+#define SBE_PUB_INVALID_LIMIT_PRICE 22u      /* "Limit price must be positive for LIMIT orders" */
+#define SBE_PUB_INVALID_STOP_PRICE 23u       /* "Stop price must be positive for STOP orders" */
+#define SBE_PUB_INVALID_STOP_LIMIT_STOP 24u  /* "Stop price must be positive for STOP_LIMIT orders" */
+#define SBE_PUB_INVALID_STOP_LIMIT_LIMIT 25u /* "Limit price must be positive for STOP_LIMIT orders" */
+#define SBE_PUB_INVALID_TIME_IN_FORCE 26u    /* "Invalid time in force: " + time_in_force */
+#define SBE_PUB_INVALID_GTD_EXPIRY 27u       /* "Expiry timestamp required for GTD orders" */
+#define SBE_PUB_INVALID_COUNT 12u
+
+/* The Order members only validate() reads (order_types.hpp:28-49), struct of arrays:
+ *   arena, str_off ([n][2] or NULL = packed), str_len [n][2]: order_type, time_in_force;
+ *   limit_price [n], stop_price [n] (f64);
+ *   present [n] u8: bit 0 = stop_price has a value, bit 1 = expiry_timestamp has a value. */
+#define SBE_PUB_HAS_STOP_PRICE 0x1u
+#define SBE_PUB_HAS_EXPIRY 0x2u
+typedef struct sbe_order_checks {
+    const uint8_t* arena;
+    const uint32_t* str_off;
+    const uint32_t* str_len;
+    const double* limit_price;
+    const double* stop_price;
+    const uint8_t* present;
+} sbe_order_checks;
+
+/* Bytes of device workspace sbe_publish_orders_batch needs for n Orders (at most 64 n + 65536:
+ * it holds sizes and offsets only, no text). */
+size_t sbe_publish_orders_workspace_size(uint64_t n);
+
+/* Upper bound of the record stream of n Orders whose Order strings total `string_bytes` (every
+ * string byte escapes to at most 6 text bytes and is printed at most three times).  A tighter
+ * size: call once with out = NULL, out_capacity = 0 and read out_off[n], which always holds the
+ * full layout. */
+uint64_t sbe_publish_orders_output_bound(uint64_t n, uint64_t string_bytes, uint32_t topic_len, int session);
+
+/* orders: as for sbe_order_to_json_batch.  checks: NULL skips validation (the caller has
+ * validated).  topic: topic_len device bytes (NULL only when topic_len is 0).  timestamp: [n]
+ * device u64 or NULL (every record takes ts_default).  session: 0 bare TopicMessage, 1 framed.
+ * out (16-B aligned; NULL with out_capacity 0 sizes only), out_off [n + 1] (8-B aligned, always
+ * the full layout), status [n] u8 or NULL, error_mask [n] u16 (2-B aligned) or NULL, workspace
+ * (16-B aligned) as for the sibling encoders.  Every argument is checked before anything is
+ * launched; n == 0 is SBE_OK with out_off[0] = 0.  On `stream`: per-block totals and their scans
+ * (packed arenas), the sizing launch, one scan, the writing launch. */
+int sbe_publish_orders_batch(const sbe_order_batch* orders, const sbe_order_checks* checks, uint64_t n,
+                             const uint8_t* topic, uint32_t topic_len, const uint64_t* timestamp,
+                             uint64_t ts_default, uint32_t flags, int session, int64_t leadership_term_id,
+                             int64_t cluster_session_id, uint8_t* out, uint64_t out_capacity, uint64_t* out_off,
+                             uint8_t* status, uint16_t* error_mask, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 /* ======================= multi-GPU gather of encoded shards (RCCL) ======================= */
 /* A batch sharded over the GPUs of one node (records [lo_r, hi_r) on rank r, contiguous, in rank

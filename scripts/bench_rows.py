@@ -7,6 +7,9 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
   session_fixed256       1 M session-framed Order TopicMessages (32-B SessionMessageHeader + 248 B)
   lite301 / lite201      1 M CommitOffsetLite / OrderRequestLite records, encode + Lite decode
   order_json             1 M Orders → Order::to_json payload + publish_order headers JSON (two calls)
+  publish_orders         1 M Orders → session-framed REF-mode wire records in one fused call
+                         (sbe_publish_orders_batch), and in the same run the composed path it replaces:
+                         the two order_json calls plus sbe_encode_session_batch on prepared offsets
   reassemble             1 M Aeron fragments (90 % whole messages, the rest BEGIN..END groups),
                          BEGIN/END reassembly (all its launches, torch events around the call)
   materialize            1 M fixed-256 records' parse_message views copied into one arena
@@ -355,6 +358,99 @@ def _event_ms(fn, steps, warmup):
     return e0.elapsed_time(e1) / steps
 
 
+def row_publish_orders(steps, warmup):
+    """publish_order for 1 M realistic Orders, session-framed, REF mode: the fused call
+    (sbe_publish_orders_batch, validation included) and, in the same run, the composed path (two
+    sbe_order_to_json_batch calls, then sbe_encode_session_batch over a prepared 5-field offset table
+    into an arena that already holds both texts), device time only (torch events).  Bytes of the
+    fused call: Order strings (uuid / base read twice, message_id and id twice, status), checks
+    strings, 32 + 24 + 8 + 24 B of lengths and numbers read, records + offsets + status + mask
+    written; the composed path moves the two texts three times more (written, read, written)."""
+    n = 1_000_000
+    fields, cid, ts, q = T.realistic_orders(n)
+    arena, str_len = T.pack_order_fields(fields)
+    topic = b"orders"
+    tm_ts = (1_760_000_000_000_000_000 + np.arange(n)).astype(np.int64)
+    args0 = (dev(arena, torch.uint8), dev(str_len.astype(np.int32), torch.int32), dev(cid, torch.int64),
+             dev(ts, torch.int64), torch.from_numpy(q).cuda())
+    topic_d = dev(np.frombuffer(topic, np.uint8), torch.uint8)
+    chk0 = (dev(np.frombuffer(b"LIMITGTC" * n, np.uint8), torch.uint8),
+            dev(np.tile(np.array([5, 3], np.int32), n), torch.int32), torch.ones(n, dtype=torch.float64, device="cuda"),
+            torch.zeros(n, dtype=torch.float64, device="cuda"), torch.zeros(n, dtype=torch.uint8, device="cuda"))
+    tm0 = dev(tm_ts, torch.int64)
+
+    def make(k):
+        args = tuple(x.clone() for x in args0)
+        chk = tuple(x.clone() for x in chk0)
+        tm = tm0.clone()
+        fused = sbecodec.publish_orders_batch(*args, topic_d, checks=chk, tm_timestamp=tm, leadership_term_id=7,
+                                              cluster_session_id=9)
+        P = sbecodec.order_to_json_batch(*args, what=sbecodec.JSON_ORDER_PAYLOAD)
+        H = sbecodec.order_to_json_batch(*args, what=sbecodec.JSON_PUBLISH_HEADERS)
+        # prepared once: topic, messageType, message ids and both texts in one arena, [n][5] offsets
+        pt, ht = int(P.out_off[-1]), int(H.out_off[-1])
+        ids = np.frombuffer(b"".join(f[6] for f in fields), np.uint8)
+        idl = str_len[:, 6].astype(np.int64)
+        big = torch.cat([topic_d, dev(np.frombuffer(b"CREATE_ORDER", np.uint8), torch.uint8), dev(ids, torch.uint8),
+                         P.out[:pt], H.out[:ht]])
+        b_ids = len(topic) + 12
+        b_pay = b_ids + ids.size
+        po, ho = P.out_off.cpu().numpy(), H.out_off.cpu().numpy()
+        off, ln = np.zeros((n, 5), np.int64), np.zeros((n, 5), np.int64)
+        ln[:, 0], off[:, 1], ln[:, 1] = len(topic), len(topic), 12
+        off[:, 2], ln[:, 2] = b_ids + np.cumsum(idl) - idl, idl
+        off[:, 3], ln[:, 3] = b_pay + po[:-1], np.diff(po)
+        off[:, 4], ln[:, 4] = b_pay + pt + ho[:-1], np.diff(ho)
+        enc_in = (big, dev(ln.astype(np.int32), torch.int32), tm)
+        enc_off = dev(off.astype(np.uint32).view(np.int32), torch.int32)
+        # topic and messageType are shared by all records, so the arena size does not bound the stream
+        enc = sbecodec.encode_session_batch(*enc_in, 7, 9, str_off=enc_off,
+                                            out=torch.empty(int(fused.out_off[-1]) + 64, dtype=torch.uint8, device="cuda"))
+        ws = torch.empty(sbecodec.publish_orders_workspace_size(n), dtype=torch.uint8, device="cuda")
+        return args, chk, tm, (fused, ws), P, H, enc_in, enc_off, enc
+
+    R = Rot(make)
+    torch.cuda.synchronize()
+    _, _, _, (fused0, _), P0, H0, _, _, enc0 = R.sets[0]
+    total = int(fused0.out_off[-1])
+    # the two paths produce the same stream
+    assert total == int(enc0.out_off[-1]) and torch.equal(fused0.out[:total], enc0.out[:total])
+    assert int(fused0.status[:n].max()) == 0 and int(enc0.status[:n].max()) == 0
+
+    def fused_fn():
+        args, chk, tm, (f, ws), *_ = R.next()
+        sbecodec.publish_orders_batch(*args, topic_d, checks=chk, tm_timestamp=tm, leadership_term_id=7,
+                                      cluster_session_id=9, out=f.out, out_off=f.out_off, status=f.status,
+                                      error_mask=f.error_mask, workspace=ws)
+
+    def composed_fn():
+        args, _, _, _, P, H, enc_in, enc_off, enc = R.next()
+        sbecodec.order_to_json_batch(*args, what=sbecodec.JSON_ORDER_PAYLOAD, out=P.out, out_off=P.out_off,
+                                     status=P.status)
+        sbecodec.order_to_json_batch(*args, what=sbecodec.JSON_PUBLISH_HEADERS, out=H.out, out_off=H.out_off,
+                                     status=H.status)
+        sbecodec.encode_session_batch(*enc_in, 7, 9, str_off=enc_off, out=enc.out, out_off=enc.out_off,
+                                      status=enc.status, workspace=enc.workspace)
+
+    ms_f = _event_ms(fused_fn, steps, warmup)
+    ms_c = _event_ms(composed_fn, steps, warmup)
+    ms_f2 = _event_ms(fused_fn, steps, warmup)  # again after the composed path: drift between the two shows here
+    text = int(P0.out_off[-1]) + int(H0.out_off[-1])
+    sl = str_len.astype(np.int64)
+    strings = int(2 * sl[:, 0].sum() + sl[:, 1:5].sum() + sl[:, 2].sum() + 2 * sl[:, 5:7].sum() + 2 * sl[:, 7].sum())
+    nb_f = strings + 8 * n + n * (32 + 24 + 8 + 8 + 17) + total + n * (8 + 1 + 2)
+    nb_c = nb_f + 3 * text
+    if max(ms_f, ms_f2) > ms_c:  # the row's condition: the fused call is not slower than the path it replaces
+        print(f"WARNING publish_orders: fused {ms_f:.4f} / {ms_f2:.4f} ms is slower than composed {ms_c:.4f} ms",
+              file=sys.stderr, flush=True)
+    print(json.dumps({"row": "publish_orders", "fused_not_slower_than_composed": bool(max(ms_f, ms_f2) <= ms_c),
+                      "composed_over_fused": ms_c / ms_f}), flush=True)
+    line("publish_orders", n, ms_f * 1e-3,
+         {"sbe_publish_orders_batch (fused: all launches)": (ms_f, nb_f),
+          "sbe_publish_orders_batch (fused, measured again after the composed path)": (ms_f2, nb_f),
+          "composed: sbe_order_to_json_batch x2 + sbe_encode_session_batch (prepared offsets)": (ms_c, nb_c)})
+
+
 def row_autocommit(steps, warmup):
     """sbe_classify_commits after a parse_message decode, three 1 M-record batches: fixed-256 Orders
     (no source holds "topic" or a backslash: no record is parsed), the config-3 mix, and fixed-256
@@ -406,7 +502,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,materialize,autocommit")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -429,6 +525,8 @@ def main():
             row_reassemble(args.steps, args.warmup)
         elif r == "order_json":
             row_order_json(args.steps, args.warmup)
+        elif r == "publish_orders":
+            row_publish_orders(args.steps, args.warmup)
         elif r == "materialize":
             row_materialize(args.steps, args.warmup)
         elif r == "autocommit":
