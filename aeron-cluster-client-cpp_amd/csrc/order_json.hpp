@@ -1129,15 +1129,18 @@ __device__ __forceinline__ void write_staged(uint8_t* out, lw8* win, uint32_t la
         __syncthreads();
         const uint64_t nch = (cend - wbase + 15) / 16;
         for (uint64_t c = lane; c < nch; c += kWWave) {
-            const uint64_t x0 = wbase + 16 * c;  // output coordinate of this 16-byte chunk
-            if (x0 >= start && x0 + 16 <= cend) {
+            // output coordinate of this 16-byte chunk; signed: when `out` is not 16-byte aligned the
+            // first window starts up to 15 bytes before out[0] (wbase = start - 1 .. start - 15 < 0)
+            const int64_t x0 = (int64_t)(wbase + 16 * c);
+            if (x0 >= (int64_t)start && x0 + 16 <= (int64_t)cend) {
                 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                 typedef const __attribute__((address_space(3))) u32x4 lu128;
                 const u32x4 v = *(lu128*)(win + 16 * c);
                 // out + x0 is 16-byte aligned (wbase's choice): one dwordx4 store a chunk
                 __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(out + x0));
             } else {
-                for (uint64_t x = x0 < start ? start : x0; x < x0 + 16 && x < cend; ++x) out[x] = win[x - wbase];
+                for (int64_t x = x0 < (int64_t)start ? (int64_t)start : x0; x < x0 + 16 && x < (int64_t)cend; ++x)
+                    out[x] = win[(uint64_t)x - wbase];
             }
         }
         __syncthreads();

@@ -751,7 +751,13 @@ __device__ __forceinline__ TileSt tile_prepare_at(const EncArgs& a, const TileIn
     S.tid = x.tid;
     const uint32_t re = S.rs + rec_out;
     const uint64_t cap_rel64 = a.cap > base_out ? a.cap - base_out : 0ull;
-    const uint32_t cap_rel = cap_rel64 < (uint64_t)agg_out ? (uint32_t)cap_rel64 : agg_out;
+    uint32_t cap_rel = agg_out;
+    if (cap_rel64 < (uint64_t)agg_out) {  // uniform: the capacity ends inside this tile (or before it)
+        // SBE_ENC_OVERFLOW writes nothing: the tile is clipped at the start of the first record that
+        // ends past the capacity (the end of the last one that fits), not at the capacity itself
+        const uint64_t over = __ballot(q == 0 && rec_out != 0 && (uint64_t)re > cap_rel64);
+        cap_rel = lane_u32(S.rs, __builtin_ctzll(over));  // over != 0: agg_out is such a record's end
+    }
     if (valid && q == 0) {
         if (st == SBE_ENC_OK && (uint64_t)re > cap_rel64) st = SBE_ENC_OVERFLOW;
         a.out_off[r] = base_out + S.rs;
@@ -4397,12 +4403,15 @@ __device__ __forceinline__ void mat_tile(const MatArgs& a, uint64_t t, const Mat
         __syncthreads();
         const uint64_t nch = (cend - wbase + 15) / 16;
         for (uint64_t c = (uint64_t)lane; c < nch; c += kWave) {
-            const uint64_t x0 = wbase + 16 * c;  // arena + x0 is 16-byte aligned
-            if (x0 >= start && x0 + 16 <= cend) {
+            // arena + x0 is 16-byte aligned; signed: the first window of an arena that is not
+            // 16-byte aligned starts up to 15 bytes before arena[0] (wbase = start - 1 .. start - 15 < 0)
+            const int64_t x0 = (int64_t)(wbase + 16 * c);
+            if (x0 >= (int64_t)start && x0 + 16 <= (int64_t)cend) {
                 const u32x4 v = *(const __attribute__((address_space(3))) u32x4*)(win + 16 * c);
                 __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(a.arena + x0));
             } else {
-                for (uint64_t x = x0 < start ? start : x0; x < x0 + 16 && x < cend; ++x) a.arena[x] = win[x - wbase];
+                for (int64_t x = x0 < (int64_t)start ? (int64_t)start : x0; x < x0 + 16 && x < (int64_t)cend; ++x)
+                    a.arena[x] = win[(uint64_t)x - wbase];
             }
         }
         __syncthreads();

@@ -7,6 +7,13 @@
  * device (or host-pinned, device-visible) pointers; `stream` is a hipStream_t passed as void*
  * (NULL = the default stream).  Nothing here allocates, synchronises or copies on the host:
  * every call is an asynchronous launch on `stream` and returns after argument validation.
+ * Every launch and memset of a call goes to `stream` and to no other stream.  A call writes the
+ * output elements its comment names and nothing else: no byte before or after an output array,
+ * and no byte outside the workspace size it asks for.
+ * Offset arrays (rec_off, frag_off) need not start at 0: they index `in`, so records a..b of a
+ * larger batch are processed by passing rec_off + a with n = b - a (and in_bytes = rec_off[b] -
+ * rec_off[a]); the per-record outputs of that call start at element 0 of the arrays it is given
+ * (status + a, view_off + 5 a, ... to fill the larger batch's arrays in place).
  *
  * Entry point                     replaces (reference)
  * ------------------------------  ------------------------------------------------------------
@@ -132,7 +139,8 @@ extern "C" {
 #define SBE_ENC_E109_UUID 3u         /* "uuidLength too long for length type [E109]" */
 #define SBE_ENC_E109_PAYLOAD 4u      /* "payloadLength too long for length type [E109]" */
 #define SBE_ENC_E109_HEADERS 5u      /* "headersLength too long for length type [E109]" */
-#define SBE_ENC_OVERFLOW 6u          /* record does not fit in out_capacity (nothing written) */
+#define SBE_ENC_OVERFLOW 6u          /* record does not fit in out_capacity (nothing written: no byte of
+                                        out from the end of the last record that fits is touched) */
 /* Lite templates: status 1 + f = "<field f>Length too long for length type [E109]" with the
  * template's field names in wire order (computeLength, e.g. CommitOffsetLite.h:839-870). */
 
@@ -310,7 +318,9 @@ int sbe_eval_sequence_numbers(const uint8_t* in, const uint64_t* rec_off, uint64
  * the last entry the total; a view of length 0, including the Lite topicId slot, takes no bytes).
  * A view that would end past arena_capacity is not written (arena_off still holds the full
  * layout, so the caller can size the arena from arena_off[5 n] and rerun); nothing is written past
- * arena_capacity.  Workspace: sbe_materialize_workspace_size(n) bytes (16-B aligned). */
+ * arena_capacity: the views written are a prefix of the layout, and the arena is untouched from
+ * the end of the last view written.  Alignment: rec_off / arena_off 8 B, views 4 B; in and arena
+ * need none.  Workspace: sbe_materialize_workspace_size(n) bytes (16-B aligned). */
 size_t sbe_materialize_workspace_size(uint64_t n);
 int sbe_materialize_views(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
                           uint8_t* arena, uint64_t arena_capacity, uint64_t* arena_off, void* workspace,
@@ -400,7 +410,9 @@ int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n,
  * at out[msg_off[m] .. msg_off[m] + carry).  counts (device u64[2]) = {m, carry}.  To continue
  * with the next batch, pass the carry bytes as its first fragment with flags 0 (a middle
  * fragment appends exactly as the accumulator would).
- * out must hold frag_off[n] - frag_off[0] bytes, msg_off n + 1 entries. */
+ * out must hold frag_off[n] - frag_off[0] bytes, msg_off n + 1 entries (entries past m, and the
+ * bytes of out past the carry, are unspecified).  Alignment: frag_off / msg_off / counts 8 B; in,
+ * flags and out need none.  Workspace: sbe_reassemble_workspace_size(n) bytes. */
 #define SBE_FRAG_BEGIN 0x80u
 #define SBE_FRAG_END 0x40u
 size_t sbe_reassemble_workspace_size(uint64_t n);
@@ -443,7 +455,8 @@ size_t sbe_order_json_workspace_size(uint64_t n);
 
 /* Write the JSON text of n Orders back to back: record i = out[out_off[i] .. out_off[i+1]).
  * out_off (n + 1 device u64) always holds the full sizes; a record past out_capacity is not
- * written and gets status SBE_JSON_OVERFLOW (status: n device u8 or NULL).  On `stream`: a
+ * written and gets status SBE_JSON_OVERFLOW (status: n device u8 or NULL).  Alignment: out_off
+ * 8 B, the Order arrays their natural alignment; out and arena need none.  On `stream`: a
  * sizing launch, a one-block scan of its per-block sums and the writing launch (packed arena:
  * first a per-block string-bytes launch and its scan). */
 int sbe_order_to_json_batch(const sbe_order_batch* in, uint64_t n, uint32_t what, uint8_t* out,
