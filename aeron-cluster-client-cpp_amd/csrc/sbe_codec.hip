@@ -4825,6 +4825,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 // after every other kernel, so that this file's earlier device code keeps its place in the code object
 #include "commit_class.hpp"
 #include "order_publish.hpp"
+#include "inflight.hpp"
 
 }  // namespace
 
@@ -5442,6 +5443,74 @@ int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n,
                  out->topic_kind, out->topic_off, out->topic_len, out->topic_idx, out->last, out->count};
         hipLaunchKernelGGL(sbe_commit_kernel, dim3((uint32_t)tiles), dim3(kWave), 0, s, a);
     }
+    return record_hip(hipGetLastError());
+}
+
+size_t sbe_inflight_table_size(uint64_t capacity) {
+    return inf_capacity_ok(capacity) ? (size_t)(64 + 64 * capacity) : 0;
+}
+
+int sbe_inflight_init(void* table, size_t table_bytes, uint64_t capacity, uint32_t tag_bits, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t need = sbe_inflight_table_size(capacity);
+    if (!table || (reinterpret_cast<uintptr_t>(table) & 63) || !need || table_bytes < need || tag_bits > 30)
+        return SBE_EINVAL;
+    if (const int rc = record_hip(hipMemsetAsync(table, 0, need, s))) return rc;
+    hipLaunchKernelGGL(inf_init_header, dim3(1), dim3(kWave), 0, s, reinterpret_cast<uint8_t*>(table), capacity,
+                       tag_bits ? tag_bits : 30u);
+    return record_hip(hipGetLastError());
+}
+
+size_t sbe_inflight_workspace_size(uint64_t n) { return (size_t)(4 * (n ? n : 1)); }
+
+int sbe_inflight_remember(void* table, const uint8_t* arena, const uint32_t* key_off, const uint32_t* key_len,
+                          uint32_t stride, const uint64_t* ts, uint64_t ts_default, const uint8_t* mask, uint64_t n,
+                          uint8_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    if (!table || mis(table, 63) || n >= (1ull << 32)) return SBE_EINVAL;
+    if (n == 0) return SBE_OK;
+    if (!arena || !key_off || !key_len || !workspace || stride == 0) return SBE_EINVAL;
+    if (mis(key_off, 3) || mis(key_len, 3) || mis(ts, 7) || mis(workspace, 3)) return SBE_EINVAL;
+    if (workspace_bytes < sbe_inflight_workspace_size(n)) return SBE_ENOSPC;
+    InfRemArgs a{reinterpret_cast<uint8_t*>(table), arena, key_off, key_len, stride, ts, ts_default, mask, n, status,
+                 reinterpret_cast<uint32_t*>(workspace)};
+    const uint32_t blocks = (uint32_t)((n + kInfBlk - 1) / kInfBlk);
+    hipLaunchKernelGGL(inf_remember_find, dim3(blocks), dim3(kInfBlk), 0, s, a);
+    hipLaunchKernelGGL(inf_remember_commit, dim3(blocks), dim3(kInfBlk), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+int sbe_inflight_match_acks(void* table, const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                            const sbe_ack_out* out, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    if (!table || mis(table, 63) || n >= (1ull << 32) || !out || mis(out->counts, 7)) return SBE_EINVAL;
+    // an empty batch only initialises counts: its per-record arrays may be null
+    if (n && (!in || !rec_off || !dec || !dec->status || !dec->ts || !dec->view_off || !dec->view_len || !out->code ||
+              !out->base_ns || !workspace))
+        return SBE_EINVAL;
+    if (n && (mis(rec_off, 7) || mis(dec->ts, 7) || mis(dec->view_off, 3) || mis(dec->view_len, 3) ||
+              mis(out->base_ns, 7) || mis(workspace, 3)))
+        return SBE_EINVAL;
+    if (n && workspace_bytes < sbe_inflight_workspace_size(n)) return SBE_ENOSPC;
+    if (out->counts)
+        if (const int rc = record_hip(hipMemsetAsync(out->counts, 0, 16, s))) return rc;
+    if (n == 0) return SBE_OK;
+    InfMatchArgs a{reinterpret_cast<uint8_t*>(table), in, rec_off, n, dec->status, dec->ts, dec->view_off,
+                   dec->view_len, out->code, out->base_ns, out->counts, reinterpret_cast<uint32_t*>(workspace)};
+    const uint32_t blocks = (uint32_t)((n + kInfBlk - 1) / kInfBlk);
+    hipLaunchKernelGGL(inf_match_find, dim3(blocks), dim3(kInfBlk), 0, s, a);
+    hipLaunchKernelGGL(inf_match_commit, dim3(blocks), dim3(kInfBlk), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+int sbe_inflight_rehash(const void* src, void* dst, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!src || !dst || src == dst || (reinterpret_cast<uintptr_t>(src) & 63) || (reinterpret_cast<uintptr_t>(dst) & 63))
+        return SBE_EINVAL;
+    hipLaunchKernelGGL(inf_rehash_kernel, dim3(kInfRehashBlocks), dim3(kInfBlk), 0, s,
+                       reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst));
     return record_hip(hipGetLastError());
 }
 

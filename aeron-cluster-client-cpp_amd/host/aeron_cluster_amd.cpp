@@ -1596,7 +1596,16 @@ std::vector<std::string> TopicPublisher::publish_topic_batch(const std::vector<T
         f[i].timestamp = (int64_t)now_nanos_sys();                         // :1845
     }
     EncodedBatch b = encode_tm(f, EncodeLength::Publish, false, 0, 0, now_nanos_sys());
-    for (size_t i = 0; i < n; ++i) (void)offer_(b.bytes.data() + b.offsets[i], b.offsets[i + 1] - b.offsets[i]);
+    std::vector<std::string> sent;
+    std::vector<uint64_t> sent_ts;
+    for (size_t i = 0; i < n; ++i) {
+        const bool ok = offer_(b.bytes.data() + b.offsets[i], b.offsets[i + 1] - b.offsets[i]);
+        if (ok && correlator_) {  // remember_outgoing(uuid, ts), src/cluster_client.cpp:1860-1861
+            sent.push_back(uuids[i]);
+            sent_ts.push_back((uint64_t)f[i].timestamp);
+        }
+    }
+    if (!sent.empty()) correlator_->remember_batch(sent, sent_ts);
     return uuids;
 }
 
@@ -2774,6 +2783,245 @@ void MessageHandler::on_egress_batch(const std::uint8_t* data, const std::uint64
             default: break;  // SBE_ST_EG_NONE
         }
     }
+}
+
+// ======================================================================================
+// AckCorrelator
+// ======================================================================================
+struct AckCorrelator::Impl {
+    hipStream_t stream = nullptr;
+    DevBuf table, in, out;  // the table; staged inputs; descriptors / results / workspace
+    uint64_t cap = 0, used_bound = 0, rehashes = 0;
+    uint32_t tag_bits = 0;
+    std::unordered_map<std::string, uint64_t> long_keys;  // keys the table cannot hold
+    std::vector<uint8_t> stage;
+
+    uint8_t* tbl() const { return reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(table.p) + 63) & ~uintptr_t(63)); }
+    static size_t al(size_t v) { return (v + 63) & ~size_t(63); }
+    void sync() { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
+    void header(uint64_t h[3]) {
+        hip_check(hipMemcpyAsync(h, tbl(), 24, hipMemcpyDeviceToHost, stream), "D2H");
+        sync();
+    }
+    // room for n more inserts below half the capacity, by rehash when needed
+    void reserve(uint64_t n) {
+        if (used_bound + n <= cap / 2) return;
+        uint64_t h[3];
+        header(h);
+        used_bound = h[2];
+        if (used_bound + n <= cap / 2) return;
+        uint64_t ncap = cap;
+        while (h[1] + n > ncap / 2) ncap *= 2;
+        if (ncap > (1ull << 31)) throw std::runtime_error("sbecodec: the in-flight table cannot grow past 2^31 slots");
+        DevBuf fresh;
+        fresh.need(sbe_inflight_table_size(ncap) + 64);
+        uint8_t* dst = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(fresh.p) + 63) & ~uintptr_t(63));
+        if (sbe_inflight_init(dst, sbe_inflight_table_size(ncap), ncap, tag_bits, stream) != SBE_OK) fail("sbe_inflight_init");
+        if (sbe_inflight_rehash(tbl(), dst, stream) != SBE_OK) fail("sbe_inflight_rehash");
+        sync();
+        std::swap(table.p, fresh.p);
+        std::swap(table.cap, fresh.cap);
+        cap = ncap;
+        used_bound = h[1];
+        ++rehashes;
+    }
+};
+
+AckCorrelator::AckCorrelator(std::uint64_t initial_capacity, std::uint32_t tag_bits) : impl_(new Impl) {
+    Impl& m = *impl_;
+    const size_t bytes = sbe_inflight_table_size(initial_capacity);
+    if (!bytes || tag_bits > 30) throw std::invalid_argument("AckCorrelator: capacity must be a power of two in 64 .. 2^31");
+    hip_check(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking), "hipStreamCreate");
+    m.cap = initial_capacity;
+    m.tag_bits = tag_bits;
+    m.table.need(bytes + 64);
+    if (sbe_inflight_init(m.tbl(), bytes, m.cap, tag_bits, m.stream) != SBE_OK) fail("sbe_inflight_init");
+    m.sync();
+}
+
+AckCorrelator::~AckCorrelator() {
+    if (impl_->stream) {
+        (void)hipStreamSynchronize(impl_->stream);
+        (void)hipStreamDestroy(impl_->stream);
+    }
+}
+
+std::uint64_t AckCorrelator::capacity() const { return impl_->cap; }
+std::uint64_t AckCorrelator::rehashes() const { return impl_->rehashes; }
+std::size_t AckCorrelator::size() const {
+    uint64_t h[3];
+    impl_->header(h);
+    return (size_t)h[1] + impl_->long_keys.size();
+}
+
+void AckCorrelator::remember_outgoing(const std::string& uuid, std::uint64_t ts_nanos) {
+    remember_batch({uuid}, {ts_nanos});
+}
+
+void AckCorrelator::remember_batch(const std::vector<std::string>& uuids, const std::vector<std::uint64_t>& ts_nanos) {
+    if (uuids.size() != ts_nanos.size()) throw std::invalid_argument("AckCorrelator::remember_batch: sizes differ");
+    Impl& m = *impl_;
+    // staged: ts [k] u64, key_off [k] u32, key_len [k] u32, key bytes
+    size_t k = 0, bytes = 0;
+    for (const std::string& u : uuids) {
+        if (u.size() <= SBE_INFLIGHT_KEY_MAX) {
+            ++k;
+            bytes += u.size();
+        }
+    }
+    const size_t o_off = 8 * k, o_len = o_off + 4 * k, o_key = o_len + 4 * k, total = o_key + bytes + 16;
+    m.stage.resize(total);
+    uint64_t* ts = reinterpret_cast<uint64_t*>(m.stage.data());
+    uint32_t* off = reinterpret_cast<uint32_t*>(m.stage.data() + o_off);
+    uint32_t* len = reinterpret_cast<uint32_t*>(m.stage.data() + o_len);
+    size_t j = 0, pos = 0;
+    for (size_t i = 0; i < uuids.size(); ++i) {
+        const std::string& u = uuids[i];
+        if (u.size() > SBE_INFLIGHT_KEY_MAX) {
+            m.long_keys.emplace(u, ts_nanos[i]);  // inflight_.emplace(uuid, ts_nanos)
+            continue;
+        }
+        ts[j] = ts_nanos[i];
+        off[j] = (uint32_t)pos;
+        len[j] = (uint32_t)u.size();
+        std::memcpy(m.stage.data() + o_key + pos, u.data(), u.size());
+        pos += u.size();
+        ++j;
+    }
+    if (!k) return;
+    if (bytes > 0xffffffffull) throw std::invalid_argument("AckCorrelator::remember_batch: more than 4 GiB of keys");
+    m.reserve(k);
+    const size_t wsb = sbe_inflight_workspace_size(k);
+    m.in.need(total);
+    m.out.need(wsb);
+    hip_check(hipMemcpyAsync(m.in.p, m.stage.data(), total, hipMemcpyHostToDevice, m.stream), "H2D");
+    // a stored ts of 0 stays 0: ts_default 0 (the reference stores what it is given)
+    if (sbe_inflight_remember(m.tbl(), m.in.b() + o_key, reinterpret_cast<const uint32_t*>(m.in.b() + o_off),
+                              reinterpret_cast<const uint32_t*>(m.in.b() + o_len), 1,
+                              reinterpret_cast<const uint64_t*>(m.in.p), 0, nullptr, k, nullptr, m.out.p, wsb,
+                              m.stream) != SBE_OK)
+        fail("sbe_inflight_remember");
+    m.sync();  // the staging buffer is reused by the next call
+    m.used_bound += k;
+}
+
+namespace {
+// Device layout of a match call's descriptors and results behind `base` (64-B aligned pieces).
+struct AckLayout {
+    size_t status, flags, hdr, ts, voff, vlen, code, base_ns, counts, ws, total;
+    explicit AckLayout(size_t n) {
+        auto al = [](size_t v) { return (v + 63) & ~size_t(63); };
+        size_t p = 0;
+        status = p, p = al(p + n);
+        flags = p, p = al(p + n);
+        hdr = p, p = al(p + 8 * n);
+        ts = p, p = al(p + 8 * n);
+        voff = p, p = al(p + 20 * n);
+        vlen = p, p = al(p + 20 * n);
+        code = p, p = al(p + n);
+        base_ns = p, p = al(p + 8 * n);
+        counts = p, p = al(p + 16);
+        ws = p, p = al(p + sbe_inflight_workspace_size(n));
+        total = p;
+    }
+};
+}  // namespace
+
+AckMatch AckCorrelator::on_ack(const AckInfo& ack, std::uint64_t now_ns) {
+    Impl& m = *impl_;
+    auto miss = [&] { return AckMatch{false, (int64_t)now_ns - (int64_t)ack.timestamp_nanos}; };
+    if (ack.message_id.empty()) return miss();
+    if (ack.message_id.size() > SBE_INFLIGHT_KEY_MAX) {
+        auto it = m.long_keys.find(ack.message_id);
+        if (it == m.long_keys.end()) return miss();
+        const uint64_t send_ns = it->second;
+        m.long_keys.erase(it);
+        return AckMatch{true, (int64_t)now_ns - (int64_t)send_ns};
+    }
+    // a one-record batch whose descriptor is written here instead of decoded: the id is the record.
+    // staged: the id bytes | rec_off [2] | the descriptor arrays of the layout (outputs follow them)
+    const AckLayout L(1);
+    const size_t idb = ack.message_id.size(), o_rec = 64, o_desc = 128;
+    m.stage.assign(o_desc + L.code, 0);
+    std::memcpy(m.stage.data(), ack.message_id.data(), idb);
+    const uint64_t rec[2] = {0, idb};
+    std::memcpy(m.stage.data() + o_rec, rec, 16);
+    m.stage[o_desc + L.status] = SBE_ST_EG_ACK;
+    std::memcpy(m.stage.data() + o_desc + L.ts, &ack.timestamp_nanos, 8);
+    const uint32_t vl = (uint32_t)idb;
+    std::memcpy(m.stage.data() + o_desc + L.vlen, &vl, 4);
+    m.in.need(o_desc + L.total);
+    hip_check(hipMemcpyAsync(m.in.p, m.stage.data(), o_desc + L.code, hipMemcpyHostToDevice, m.stream), "H2D");
+    uint8_t* d = m.in.b() + o_desc;
+    sbe_decoded dec{d + L.status, d + L.flags, reinterpret_cast<uint16_t*>(d + L.hdr), reinterpret_cast<uint64_t*>(d + L.ts),
+                    reinterpret_cast<uint32_t*>(d + L.voff), reinterpret_cast<uint32_t*>(d + L.vlen), nullptr};
+    sbe_ack_out out{d + L.code, reinterpret_cast<uint64_t*>(d + L.base_ns), nullptr};
+    if (sbe_inflight_match_acks(m.tbl(), m.in.b(), reinterpret_cast<const uint64_t*>(m.in.b() + o_rec), 1, &dec, &out,
+                                d + L.ws, sbe_inflight_workspace_size(1), m.stream) != SBE_OK)
+        fail("sbe_inflight_match_acks");
+    uint8_t code = 0;
+    uint64_t base = 0;
+    hip_check(hipMemcpyAsync(&code, d + L.code, 1, hipMemcpyDeviceToHost, m.stream), "D2H");
+    hip_check(hipMemcpyAsync(&base, d + L.base_ns, 8, hipMemcpyDeviceToHost, m.stream), "D2H");
+    m.sync();
+    return AckMatch{code == SBE_ACK_MATCHED, (int64_t)now_ns - (int64_t)base};
+}
+
+std::vector<AckMatch> AckCorrelator::on_egress_batch(const std::uint8_t* data, const std::uint64_t* rec_off,
+                                                     std::size_t n, std::uint64_t now_ns) {
+    std::vector<AckMatch> res;
+    if (!n) return res;
+    Impl& m = *impl_;
+    const AckLayout L(n);
+    const uint64_t base0 = rec_off[0], bytes = rec_off[n] - base0;
+    // staged: rec_off rebased to 0 [n + 1], then the record bytes (16-B aligned)
+    const size_t o_data = Impl::al(8 * (n + 1)), total_in = o_data + bytes + 16;
+    m.stage.resize(total_in);
+    uint64_t* ro = reinterpret_cast<uint64_t*>(m.stage.data());
+    for (size_t i = 0; i <= n; ++i) ro[i] = rec_off[i] - base0;
+    if (bytes) std::memcpy(m.stage.data() + o_data, data + base0, bytes);
+    m.in.need(total_in);
+    m.out.need(L.total);
+    hip_check(hipMemcpyAsync(m.in.p, m.stage.data(), total_in, hipMemcpyHostToDevice, m.stream), "H2D");
+    uint8_t* d = m.out.b();
+    sbe_decoded dec{d + L.status, d + L.flags, reinterpret_cast<uint16_t*>(d + L.hdr), reinterpret_cast<uint64_t*>(d + L.ts),
+                    reinterpret_cast<uint32_t*>(d + L.voff), reinterpret_cast<uint32_t*>(d + L.vlen), nullptr};
+    const uint64_t* d_ro = reinterpret_cast<const uint64_t*>(m.in.p);
+    if (sbe_decode_batch_sized(m.in.b() + o_data, d_ro, n, bytes, SBE_DEC_ON_EGRESS, &dec, m.stream) != SBE_OK)
+        fail("sbe_decode_batch");
+    sbe_ack_out out{d + L.code, reinterpret_cast<uint64_t*>(d + L.base_ns), nullptr};
+    if (sbe_inflight_match_acks(m.tbl(), m.in.b() + o_data, d_ro, n, &dec, &out, d + L.ws, sbe_inflight_workspace_size(n),
+                                m.stream) != SBE_OK)
+        fail("sbe_inflight_match_acks");
+    std::vector<uint8_t> code(n);
+    std::vector<uint64_t> base(n);
+    hip_check(hipMemcpyAsync(code.data(), d + L.code, n, hipMemcpyDeviceToHost, m.stream), "D2H");
+    hip_check(hipMemcpyAsync(base.data(), d + L.base_ns, 8 * n, hipMemcpyDeviceToHost, m.stream), "D2H");
+    m.sync();
+    // ids the table cannot hold: their views come back too, and the host map answers
+    std::vector<uint32_t> voff, vlen;
+    if (std::find(code.begin(), code.end(), (uint8_t)SBE_ACK_LONG_ID) != code.end()) {
+        voff.resize(5 * n);
+        vlen.resize(5 * n);
+        hip_check(hipMemcpyAsync(voff.data(), d + L.voff, 20 * n, hipMemcpyDeviceToHost, m.stream), "D2H");
+        hip_check(hipMemcpyAsync(vlen.data(), d + L.vlen, 20 * n, hipMemcpyDeviceToHost, m.stream), "D2H");
+        m.sync();
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (code[i] == SBE_ACK_NONE) continue;
+        bool matched = code[i] == SBE_ACK_MATCHED;
+        uint64_t b = base[i];
+        if (code[i] == SBE_ACK_LONG_ID) {
+            auto it = m.long_keys.find(std::string(reinterpret_cast<const char*>(data) + rec_off[i] + voff[5 * i], vlen[5 * i]));
+            if (it != m.long_keys.end()) {
+                matched = true;
+                b = it->second;
+                m.long_keys.erase(it);
+            }
+        }
+        res.push_back(AckMatch{matched, (int64_t)now_ns - (int64_t)b});
+    }
+    return res;
 }
 
 std::size_t offer_batch(const EncodedBatch& batch, const OfferFn& offer) {

@@ -433,6 +433,52 @@ private:
 // The raw ingress sink (ClusterClient::offer_ingress signature, include/aeron_cluster/cluster_client.hpp:409).
 using OfferFn = std::function<bool(const std::uint8_t* data, std::size_t len)>;
 
+// What ClusterClient::on_ack_default (src/cluster_client.cpp:1924-1941) computes for one ack:
+// matched: message_id was in flight (the entry is erased), rtt_ns = (int64)now - (int64)send_ns;
+// otherwise rtt_ns = (int64)now - (int64)ack.timestamp_nanos, the reference's est_rtt.
+struct AckMatch {
+    bool matched = false;
+    std::int64_t rtt_ns = 0;
+};
+
+// ClusterClient's inflight_ (include/aeron_cluster/cluster_client.hpp:420) with remember_outgoing
+// (src/cluster_client.cpp:1920-1922) and on_ack_default (:1924-1941).  State: one device table
+// (sbe_inflight_*, keys up to SBE_INFLIGHT_KEY_MAX = 40 bytes) and a host std::unordered_map for
+// longer keys; a key goes to one or the other by its length, decided on the host, so no status is
+// read back after a remember.  Before a batch that would take the table's used slots past half
+// its capacity, the table is rehashed into one with room (erased slots are reclaimed; the capacity
+// doubles as often as needed).
+// Cost: every call copies its keys / records to the device and waits for the result on a stream of
+// its own.  The single forms (remember_outgoing, on_ack) are one-record batches: two launches plus
+// the copies, tens of microseconds where the reference's map needs well under one; use them for
+// compatibility and the batch forms for throughput.  on_egress_batch decodes the records on the
+// device (sbe_decode_batch, SBE_DEC_ON_EGRESS) and matches the descriptors where they lie: only
+// a code and a time per record come back.  One thread at a time.
+class AckCorrelator {
+public:
+    explicit AckCorrelator(std::uint64_t initial_capacity = 1u << 16, std::uint32_t tag_bits = 0);
+    ~AckCorrelator();
+    AckCorrelator(const AckCorrelator&) = delete;
+    AckCorrelator& operator=(const AckCorrelator&) = delete;
+
+    void remember_outgoing(const std::string& uuid, std::uint64_t ts_nanos);
+    // remember_outgoing(uuids[i], ts[i]) for every i, in order (ts.size() == uuids.size())
+    void remember_batch(const std::vector<std::string>& uuids, const std::vector<std::uint64_t>& ts_nanos);
+    AckMatch on_ack(const AckInfo& ack, std::uint64_t now_ns);
+    // MessageHandler::on_egress over the records with on_ack_default as its ack callback: one entry
+    // per ack (simple or full), in record order; other records give none.
+    std::vector<AckMatch> on_egress_batch(const std::uint8_t* data, const std::uint64_t* rec_off, std::size_t n,
+                                          std::uint64_t now_ns);
+    // entries that can still match (reads the table's header back), table capacity, rehashes so far
+    std::size_t size() const;
+    std::uint64_t capacity() const;
+    std::uint64_t rehashes() const;
+
+private:
+    struct Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
 // ClusterClient::publish_topic (src/cluster_client.cpp:1809-1864) minus the connection checks:
 // uuid = "pub_" + now_nanos() (:1818), headers "{}" when empty (:1821), timestamp now_nanos()
 // (:1845), sequenceNumber 0, the put*(const char*, int) length wrap (EncodeLength::Publish), and
@@ -446,9 +492,14 @@ public:
     // Batch form: one GPU launch for all records, offered in order; each message gets its own uuid
     // and timestamp (msgs[i].uuid / .timestamp are ignored).  Returns the uuids.
     std::vector<std::string> publish_topic_batch(const std::vector<TopicMessageFields>& msgs);
+    // With a correlator set, every record whose offer returned true is remembered with its uuid and
+    // timestamp (src/cluster_client.cpp:1860-1861), one remember_batch per publish call; nullptr
+    // (the default): nothing is remembered.  The correlator must outlive the publisher's calls.
+    void set_correlator(AckCorrelator* correlator) { correlator_ = correlator; }
 
 private:
     OfferFn offer_;
+    AckCorrelator* correlator_ = nullptr;
 };
 
 // include/aeron_cluster/commit_manager.hpp:17-24

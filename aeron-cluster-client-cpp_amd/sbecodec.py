@@ -111,6 +111,10 @@ class _CommitOut(ctypes.Structure):
                 ("last", ctypes.c_void_p), ("count", ctypes.c_void_p)]
 
 
+class _AckOut(ctypes.Structure):
+    _fields_ = [("code", ctypes.c_void_p), ("base_ns", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise SbeError(f"{LIB_PATH} is missing: build it with `make -C aeron-cluster-client-cpp_amd` "
@@ -176,6 +180,24 @@ def _load():
                                          ctypes.POINTER(_Decoded), ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_uint32, ctypes.POINTER(_CommitOut), ctypes.c_void_p,
                                          ctypes.c_size_t, ctypes.c_void_p]
+    lib.sbe_inflight_table_size.restype = ctypes.c_size_t
+    lib.sbe_inflight_table_size.argtypes = [ctypes.c_uint64]
+    lib.sbe_inflight_workspace_size.restype = ctypes.c_size_t
+    lib.sbe_inflight_workspace_size.argtypes = [ctypes.c_uint64]
+    lib.sbe_inflight_init.restype = ctypes.c_int
+    lib.sbe_inflight_init.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32,
+                                      ctypes.c_void_p]
+    lib.sbe_inflight_remember.restype = ctypes.c_int
+    lib.sbe_inflight_remember.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                          ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.c_void_p]
+    lib.sbe_inflight_match_acks.restype = ctypes.c_int
+    lib.sbe_inflight_match_acks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                            ctypes.POINTER(_Decoded), ctypes.POINTER(_AckOut), ctypes.c_void_p,
+                                            ctypes.c_size_t, ctypes.c_void_p]
+    lib.sbe_inflight_rehash.restype = ctypes.c_int
+    lib.sbe_inflight_rehash.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.sbe_profile_enable.restype = ctypes.c_int
     lib.sbe_order_json_workspace_size.argtypes = [ctypes.c_uint64]
     lib.sbe_order_json_workspace_size.restype = ctypes.c_size_t
@@ -603,6 +625,122 @@ def classify_commits(data, rec_off, dec: Decoded, topics, out: CommitPlan | None
     if n < out.cm.numel():
         out = CommitPlan(*(getattr(out, f)[:n] for f, _ in _COMMIT_KEYS[:6]), out.last, out.count)
     return out
+
+
+# sbe_inflight_*: ack correlation (include/sbecodec.h)
+INF_INSERTED, INF_DUPLICATE, INF_SKIPPED, INF_KEY_TOO_LONG, INF_FULL = range(5)
+ACK_NONE, ACK_MATCHED, ACK_UNMATCHED, ACK_LONG_ID = range(4)
+INFLIGHT_KEY_MAX = 40
+
+
+@dataclass
+class AckMatches:
+    code: torch.Tensor     # uint8 [n]  ACK_*
+    base_ns: torch.Tensor  # int64 [n]  (u64) what on_ack_default subtracts from now_nanos()
+    counts: torch.Tensor   # int64 [2]  (u64) matched, acks not matched
+
+    def numpy(self):
+        import numpy as np
+        return {"code": self.code.cpu().numpy(), "base_ns": self.base_ns.cpu().numpy().view(np.uint64),
+                "counts": self.counts.cpu().numpy().view(np.uint64)}
+
+
+class Inflight:
+    """The in-flight table of ClusterClient (remember_outgoing / on_ack_default,
+    src/cluster_client.cpp:1920-1941) on the device: `capacity` slots (a power of two, 64 .. 2^31)
+    of 64 bytes.  It owns the table tensor and sizes its own workspace; it serves one stream at a
+    time.  tag_bits: see sbe_inflight_init (results do not depend on it)."""
+
+    def __init__(self, capacity: int, device, tag_bits: int = 0, stream=None, table=None):
+        size = int(lib().sbe_inflight_table_size(int(capacity)))
+        if size == 0:
+            raise SbeError(f"Inflight: capacity {capacity} is not a power of two in 64 .. 2^31")
+        self.capacity, self.tag_bits, self.device = int(capacity), int(tag_bits), torch.device(device)
+        if table is not None:  # the caller's memory (uint8, 64-byte aligned, at least table_bytes(capacity))
+            self.table = _dev(table, torch.uint8, "table")[:size]
+        else:
+            raw = torch.empty(size + 64, dtype=torch.uint8, device=self.device)
+            lead = (-raw.data_ptr()) % 64
+            self.table = raw[lead: lead + size]
+        self._ws = None
+        self.clear(stream)
+
+    @staticmethod
+    def table_bytes(capacity: int) -> int:
+        return int(lib().sbe_inflight_table_size(int(capacity)))
+
+    def clear(self, stream=None):
+        """Back to an empty table (sbe_inflight_init)."""
+        _check(lib().sbe_inflight_init(_ptr(self.table), int(self.table.numel()), self.capacity, self.tag_bits,
+                                       _stream(stream)), "sbe_inflight_init")
+
+    def _workspace(self, n, workspace):
+        need = int(lib().sbe_inflight_workspace_size(n))
+        if workspace is not None:
+            return _dev(workspace, torch.uint8, "workspace")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def remember(self, arena, key_off, key_len, ts=None, ts_default=0, mask=None, stride=1, stream=None,
+                 status=None, workspace=None, n=None) -> torch.Tensor:
+        """remember_outgoing for n records in order: key i = arena[key_off[i*stride]:][:key_len[i*stride]]
+        (int32 tensors holding u32), ts int64 [n] (0 / None: ts_default), mask uint8 [n] (0: the offer
+        failed).  n defaults to ceil(len(key_len) / stride).  Returns the status tensor (INF_*)."""
+        arena = _dev(arena, torch.uint8, "arena")
+        key_off = _dev(key_off, torch.int32, "key_off")
+        key_len = _dev(key_len, torch.int32, "key_len")
+        ts = _dev(ts, torch.int64, "ts")
+        mask = _dev(mask, torch.uint8, "mask")
+        if n is None:
+            n = -(-int(key_len.numel()) // int(stride))
+        if arena.numel() == 0:
+            arena = torch.zeros(16, dtype=torch.uint8, device=self.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        ws = self._workspace(n, workspace)
+        rc = lib().sbe_inflight_remember(_ptr(self.table), _ptr(arena), _ptr(key_off), _ptr(key_len), int(stride),
+                                         _ptr(ts), int(ts_default), _ptr(mask), n, _ptr(status), _ptr(ws),
+                                         int(ws.numel()), _stream(stream))
+        _check(rc, "sbe_inflight_remember")
+        return status[:n]
+
+    def match_acks(self, data, rec_off, dec: Decoded, stream=None, out: AckMatches | None = None,
+                   workspace=None) -> AckMatches:
+        """on_ack_default for the records of a decode_batch(mode=DEC_ON_EGRESS) on the same data /
+        rec_off, in order: code (ACK_*), base_ns and counts {matched, not matched}."""
+        data = _dev(data, torch.uint8, "data")
+        rec_off = _dev(rec_off, torch.int64, "rec_off")
+        n = int(rec_off.numel()) - 1
+        if data.numel() == 0:
+            data = torch.zeros(16, dtype=torch.uint8, device=self.device)
+        if out is None:
+            out = AckMatches(torch.empty(max(n, 1), dtype=torch.uint8, device=self.device),
+                             torch.empty(max(n, 1), dtype=torch.int64, device=self.device),
+                             torch.empty(2, dtype=torch.int64, device=self.device))
+        ws = self._workspace(n, workspace)
+        d = _Decoded(*(getattr(dec, f).data_ptr() for f in ("status", "flags", "hdr", "ts", "view_off", "view_len")))
+        o = _AckOut(out.code.data_ptr(), out.base_ns.data_ptr(), out.counts.data_ptr())
+        rc = lib().sbe_inflight_match_acks(_ptr(self.table), _ptr(data), _ptr(rec_off), n, ctypes.byref(d),
+                                           ctypes.byref(o), _ptr(ws), int(ws.numel()), _stream(stream))
+        _check(rc, "sbe_inflight_match_acks")
+        if n < out.code.numel():
+            out = AckMatches(out.code[:n], out.base_ns[:n], out.counts)
+        return out
+
+    def stats(self) -> dict:
+        """{capacity, live, used} read back from the table's header (synchronises)."""
+        h = self.table[:24].cpu().numpy().view("<u8")
+        return {"capacity": int(h[0]), "live": int(h[1]), "used": int(h[2])}
+
+    def rehash(self, capacity: int, stream=None, tag_bits=None) -> "Inflight":
+        """A new table of `capacity` slots holding this one's live entries (erased slots reclaimed)."""
+        live = self.stats()["live"]
+        if live >= capacity:
+            raise SbeError(f"Inflight.rehash: {live} live entries do not fit {capacity} slots")
+        new = Inflight(capacity, self.device, self.tag_bits if tag_bits is None else tag_bits, stream=stream)
+        _check(lib().sbe_inflight_rehash(_ptr(self.table), _ptr(new.table), _stream(stream)), "sbe_inflight_rehash")
+        return new
 
 
 @dataclass

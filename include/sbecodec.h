@@ -61,6 +61,13 @@
  *                                  create_topic_message and the session frame
  *                                  src/session_manager.cpp:1050-1144 (sbe_publish_orders_workspace_size,
  *                                  sbe_publish_orders_output_bound size its buffers)
+ * sbe_inflight_remember()         ClusterClient::remember_outgoing src/cluster_client.cpp:1920-1922 for
+ *                                  the records publish_topic offered (:1860-1861): the emplace into
+ *                                  inflight_ (include/aeron_cluster/cluster_client.hpp:420)
+ * sbe_inflight_match_acks()       ClusterClient::on_ack_default src/cluster_client.cpp:1924-1941, the
+ *                                  ack callback wired at :1648: find / erase in inflight_ and the time
+ *                                  the round trip is measured from (sbe_inflight_init, _rehash,
+ *                                  _table_size, _workspace_size manage the device table)
  * sbe_serve_*()                   the same encoders / decoders for small batches (one record per
  *                                  call, as the reference's per-message API is used: parse_message per
  *                                  fragment src/cluster_client.cpp:1185, publish_topic per message)
@@ -397,6 +404,99 @@ size_t sbe_commit_workspace_size(uint64_t n, uint32_t k);
 int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
                          const uint8_t* topic_arena, const uint32_t* topic_off, uint32_t k,
                          const sbe_commit_out* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ================================= ack correlation ================================= */
+/* The step of the client's message loop that joins the two directions: publish_topic remembers
+ * every offered record (remember_outgoing(uuid, ts), src/cluster_client.cpp:1860-1861, :1920-1922,
+ * an emplace into std::unordered_map<std::string, std::uint64_t> inflight_,
+ * include/aeron_cluster/cluster_client.hpp:420), and on_ack_default (:1924-1941) looks every ack's
+ * message_id up there: found, it erases the entry and reports now - send_ns; not found, now -
+ * ack.timestamp_nanos.  Here both run on whole batches against a hash table in caller-owned
+ * device memory that lives across calls.
+ *
+ * The table: sbe_inflight_table_size(capacity) bytes, 64-B aligned; one 64-B header, then
+ * `capacity` slots of 64 B; capacity a power of two, 64 .. 2^31.  The header's first words, for a
+ * caller that reads them with its own copy:
+ *   +0 u64 capacity   +8 u64 live (entries that can still match)
+ *   +16 u64 used (slots that are not empty, erased ones included)   +24 u32 tag_bits
+ * Limits: keys are stored inline, zero-padded, up to SBE_INFLIGHT_KEY_MAX bytes (the reference's
+ * "pub_" + now_nanos() is at most 24); a longer key is reported, not stored (the host mirror keeps
+ * those in a map of its own).  Erased slots are not reused by inserts: sbe_inflight_rehash into a
+ * fresh table reclaims them.  A table serves one stream at a time; calls take effect in stream
+ * order.  The header is device memory, which the host does not read: a null or misaligned table is
+ * SBE_EINVAL, while a table whose header is not one sbe_inflight_init wrote is found on the device,
+ * which then treats it as holding nothing and having no room (every remembered record SBE_INF_FULL,
+ * no ack matched, a rehash copies nothing) and leaves it untouched. */
+#define SBE_INFLIGHT_KEY_MAX 40u
+/* status[i] of sbe_inflight_remember */
+#define SBE_INF_INSERTED 0u     /* the record was stored */
+#define SBE_INF_DUPLICATE 1u    /* the key was live already, or a smaller index of this call has it;
+                                   the stored ts is unchanged (emplace) */
+#define SBE_INF_SKIPPED 2u      /* mask[i] was 0: the offer failed (:1860) */
+#define SBE_INF_KEY_TOO_LONG 3u /* over SBE_INFLIGHT_KEY_MAX bytes: not stored */
+#define SBE_INF_FULL 4u         /* no free slot was found */
+/* code[i] of sbe_inflight_match_acks */
+#define SBE_ACK_NONE 0u      /* status is neither SBE_ST_EG_ACK_SIMPLE nor SBE_ST_EG_ACK: no ack callback */
+#define SBE_ACK_MATCHED 1u   /* a non-empty id was found live; the entry is erased and `live` drops */
+#define SBE_ACK_UNMATCHED 2u /* the id is empty (every simple ack) or was not found */
+#define SBE_ACK_LONG_ID 3u   /* the id is over SBE_INFLIGHT_KEY_MAX bytes: it cannot be in the table */
+
+/* 64 + 64 * capacity; 0 if capacity is not a power of two in 64 .. 2^31. */
+size_t sbe_inflight_table_size(uint64_t capacity);
+
+/* Make `table` (table_bytes >= sbe_inflight_table_size(capacity)) an empty table: a memset and a
+ * one-wave launch on `stream`.  tag_bits (1..30, 0 = 30): the hash bits a slot keeps as a filter
+ * in front of the comparison of the key bytes; results are the same for every value (1 makes every
+ * probe of an occupied slot reach the byte comparison half of the time, 30 next to never).
+ * SBE_EINVAL: null or misaligned table, bad capacity, table_bytes too small, tag_bits > 30. */
+int sbe_inflight_init(void* table, size_t table_bytes, uint64_t capacity, uint32_t tag_bits, void* stream);
+
+/* Workspace bytes of sbe_inflight_remember and sbe_inflight_match_acks for n records (4-B aligned). */
+size_t sbe_inflight_workspace_size(uint64_t n);
+
+/* remember_outgoing for records 0 .. n-1, in order.  Key i is arena[key_off[i*stride] ..) with
+ * key_len[i*stride] bytes (str_off + 2, str_len + 2, stride 5: the uuid column of an sbe_tm_batch
+ * with explicit offsets); ts[i] is the send time, 0 or ts == NULL: ts_default (the encoders' rule,
+ * so the same arrays serve both); mask: NULL or u8[n], 0 = the offer failed, the record is
+ * skipped.  emplace semantics: the first record of a key wins, against the table's live entries
+ * and against smaller indices of the same call.  An empty key is stored like any other.
+ * status: [n] u8 or NULL.  With used + n < capacity no record is SBE_INF_FULL and every status and
+ * the table's content are those of the sequential loop (it is enough that used + the number of
+ * distinct new keys of the call stays below capacity).  Otherwise which records are SBE_INF_FULL
+ * is unspecified, but every record gets exactly one status, exactly the SBE_INF_INSERTED ones were
+ * added, and after a call that reported SBE_INF_FULL used == capacity.
+ * Two launches on `stream`.  SBE_EINVAL (before any launch): a null table / arena / key_off /
+ * key_len / workspace, stride 0, n >= 2^32, table not 64-B, ts not 8-B, key_off / key_len /
+ * workspace not 4-B aligned; SBE_ENOSPC: workspace too small.  n == 0 is SBE_OK. */
+int sbe_inflight_remember(void* table, const uint8_t* arena, const uint32_t* key_off, const uint32_t* key_len,
+                          uint32_t stride, const uint64_t* ts, uint64_t ts_default, const uint8_t* mask,
+                          uint64_t n, uint8_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+typedef struct sbe_ack_out {
+    uint8_t* code;     /* [n] SBE_ACK_* */
+    uint64_t* base_ns; /* [n] what on_ack_default subtracts from now_nanos(): the remembered send time
+                          (MATCHED) or the ack's timestamp_nanos (otherwise); 0 for SBE_ACK_NONE */
+    uint64_t* counts;  /* [2] {matched, acks not matched (UNMATCHED + LONG_ID)}, set by the call
+                          itself; or NULL */
+} sbe_ack_out;
+
+/* on_ack_default for a batch decoded with sbe_decode_batch(SBE_DEC_ON_EGRESS) on the same in /
+ * rec_off (dec: its status, ts, view_off, view_len), in record order; the id is view 0 of a full
+ * ack.  Erase-on-match is sequential: of several acks of one call with the same id only the
+ * smallest index matches, the others are SBE_ACK_UNMATCHED (the first one erased the entry).
+ * A memset of counts and two launches on `stream`.  SBE_EINVAL as for sbe_inflight_remember (out,
+ * code, base_ns, in, rec_off, dec and its four arrays must not be null; rec_off / ts / base_ns /
+ * counts 8-B, view arrays 4-B aligned).  n == 0 is SBE_OK with counts = {0, 0}: only table, out
+ * and counts are looked at. */
+int sbe_inflight_match_acks(void* table, const uint8_t* in, const uint64_t* rec_off, uint64_t n,
+                            const sbe_decoded* dec, const sbe_ack_out* out, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* Copy the live entries of src, each with its ts, into dst, an initialised empty table of any
+ * capacity with room: the caller checks live(src) < capacity(dst) from the header words (entries
+ * that find no slot are dropped).  src is unchanged; used(dst) == live(src) afterwards.  One launch
+ * on `stream`.  SBE_EINVAL: null, misaligned or identical tables. */
+int sbe_inflight_rehash(const void* src, void* dst, void* stream);
 
 /* ============================ Aeron fragment reassembly ============================ */
 /* Replaces LocalFragmentReassembler::onFragment (src/cluster_client.cpp:39-82) for a batch of

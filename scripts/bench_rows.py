@@ -14,6 +14,10 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
                          BEGIN/END reassembly (all its launches, torch events around the call)
   materialize            1 M fixed-256 records' parse_message views copied into one arena
                          (sbe_materialize_views, all its launches, torch events around the call)
+  ack_correlate          1 M "pub_<nanos>" uuids remembered in a 2 M-slot in-flight table, then 1 M full
+                         acks (about 10 % unknown ids, 1 % repeated ids) decoded on-egress and matched;
+                         remember, match and the decode of the same ack batch timed in the same run, and
+                         a one-thread std::unordered_map doing the same sequence on the host
 Rows whose buffers fit the 256 MB MALL a few times over rotate over --rotate (3) copies of their
 inputs and outputs (step k uses copy k mod R), as bench.py does, so no step finds its inputs in the
 cache a previous step left them in; config 4's 16.8 M-record batch (~6.5 GB) needs no rotation.
@@ -498,11 +502,100 @@ def row_autocommit(steps, warmup):
         torch.cuda.empty_cache()
 
 
+def row_ack_correlate(steps, warmup):
+    """sbe_inflight_remember of 1 M publish_topic uuids into an empty 2 M-slot table, then
+    sbe_inflight_match_acks of 1 M full acks (T.ack_wire; about 10 % ids nobody sent, 1 % ids that
+    appeared earlier in the batch), with sbe_decode_batch(ON_EGRESS) of the same ack buffers timed in
+    the same run.  Every step starts from an empty table (sbe_inflight_init, not timed).  Bytes,
+    per record: remember reads the key (23), offset, length and ts (16), writes a status and a
+    workspace word twice (9) and reads and writes one 64-B slot twice (launch A probes it, launch B
+    fills it); match reads the id (23) and 25 B of descriptors, writes code and base_ns (9), the
+    workspace word twice (8) and reads one slot twice.  The slot accesses are random 64-B lines: the
+    row is latency-bound and these fractions of the HBM peak say how far from a stream it is.
+    CPU: tests/inflight/map_baseline, one thread, the same emplace / find / erase sequence."""
+    import subprocess
+    n, cap = 1_000_000, 1 << 21
+    rng = np.random.default_rng(0x5EED09)
+    base = 1_760_000_000_000_000_000
+    nanos = base + np.cumsum(rng.integers(1, 2000, n)).astype(np.int64)
+    keys = np.frombuffer(b"".join(b"pub_%d" % v for v in nanos), np.uint8)
+    assert keys.size == 23 * n
+    key_off = (23 * np.arange(n)).astype(np.int32)
+    key_len = np.full(n, 23, np.int32)
+    send_ts = nanos.copy()
+    # the acks: a shuffled 89 % of the sent ids, 10 % strangers, 1 % repeats of an earlier ack of the batch
+    kind = rng.random(n)
+    ids = nanos[rng.permutation(n)]
+    strangers = kind < 0.10
+    ids[strangers] = base - 1 - rng.integers(0, 10 ** 9, int(strangers.sum()))
+    rep = np.nonzero(kind > 0.99)[0]
+    rep = rep[rep > 0]
+    ids[rep] = ids[(rep * rng.random(rep.size)).astype(np.int64)]
+    recs = [T.ack_wire(b"pub_%d" % v, b"orders", b"c", base + 5) + b"\0" * 8 for v in ids]  # len - 8: see ack_decoder.cpp:67
+    data, off = T.pack_records(recs)
+    k0, o0, l0, t0 = dev(keys, torch.uint8), dev(key_off, torch.int32), dev(key_len, torch.int32), dev(send_ts, torch.int64)
+    d0, r0 = dev(data, torch.uint8), dev(off, torch.int64)
+
+    def make(k):
+        tbl = sbecodec.Inflight(cap, "cuda")
+        d, r = d0.clone(), r0.clone()
+        dec = sbecodec.decode_batch(d, r, sbecodec.DEC_ON_EGRESS, out=sbecodec.alloc_decoded(n, "cuda"), in_bytes=data.size)
+        st = tbl.remember(k0, o0, l0, t0)
+        res = tbl.match_acks(d, r, dec)
+        return tbl, k0.clone(), o0.clone(), l0.clone(), t0.clone(), d, r, dec, st, res
+    R = Rot(make)
+    torch.cuda.synchronize()
+    st0, res0 = R.sets[0][8], R.sets[0][9].numpy()
+    assert int(st0.max()) == sbecodec.INF_INSERTED  # nanos are strictly increasing: no duplicate key
+    codes = np.bincount(res0["code"], minlength=4).tolist()
+    # the model: a dict over the same sequence
+    sent = dict(zip(nanos.tolist(), send_ts.tolist()))
+    exp = np.array([sbecodec.ACK_MATCHED if sent.pop(v, None) is not None else sbecodec.ACK_UNMATCHED for v in ids.tolist()])
+    assert np.array_equal(res0["code"], exp) and codes[1] == int(res0["counts"][0])
+
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(steps)]
+    def step(e):
+        tbl, k, o, l, t, d, r, dec, st, res = R.next()
+        tbl.clear()
+        if e:
+            e[0].record()
+        tbl.remember(k, o, l, t, status=st)
+        if e:
+            e[1].record()
+        sbecodec.decode_batch(d, r, sbecodec.DEC_ON_EGRESS, out=dec, in_bytes=data.size)
+        if e:
+            e[2].record()
+        tbl.match_acks(d, r, dec, out=res)
+        if e:
+            e[3].record()
+    for _ in range(warmup):
+        step(None)
+    torch.cuda.synchronize()
+    for e in ev:
+        step(e)
+    torch.cuda.synchronize()
+    t = np.array([[e[j].elapsed_time(e[j + 1]) for j in range(3)] for e in ev])
+    ms_rem, ms_dec, ms_match = (float(v) for v in np.median(t, axis=0))
+    kernels = {"sbe_inflight_remember (2 launches)": (ms_rem, (23 + 16 + 9 + 4 * 64) * n),
+               "sbe_inflight_match_acks (memset + 2 launches)": (ms_match, (23 + 25 + 9 + 8 + 2 * 64) * n),
+               "sbe_decode_batch ON_EGRESS (same ack buffers, same run)": (ms_dec, int(off[-1]) + 8 * n + DESC * n)}
+    extra = {"row": "ack_correlate", "codes_none_matched_unmatched_long": codes, "capacity": cap,
+             "ms_min": {"remember": float(t[:, 0].min()), "decode": float(t[:, 1].min()), "match": float(t[:, 2].min())},
+             "match_over_decode": ms_match / ms_dec}
+    if not NO_CPU:
+        d = os.path.join(ROOT, "tests", "inflight")
+        subprocess.run(["make", "-s", "-C", d, "map_baseline"], check=True)
+        extra["cpu_unordered_map_one_thread"] = json.loads(subprocess.run([os.path.join(d, "map_baseline"), str(n)], check=True,
+                                                                           capture_output=True, text=True).stdout)
+    print(json.dumps(extra), flush=True)
+    line("ack_correlate", n, (ms_rem + ms_match) * 1e-3, kernels)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,ack_correlate")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -531,6 +624,8 @@ def main():
             row_materialize(args.steps, args.warmup)
         elif r == "autocommit":
             row_autocommit(args.steps, args.warmup)
+        elif r == "ack_correlate":
+            row_ack_correlate(args.steps, args.warmup)
         elif r.startswith("lite"):
             row_lite(int(r[4:]), args.steps, args.warmup)
         torch.cuda.empty_cache()
