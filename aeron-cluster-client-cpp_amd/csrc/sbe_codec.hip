@@ -4826,6 +4826,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 #include "commit_class.hpp"
 #include "order_publish.hpp"
 #include "inflight.hpp"
+#include "commit_emit.hpp"
 
 }  // namespace
 
@@ -5443,6 +5444,69 @@ int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n,
                  out->topic_kind, out->topic_off, out->topic_len, out->topic_idx, out->last, out->count};
         hipLaunchKernelGGL(sbe_commit_kernel, dim3((uint32_t)tiles), dim3(kWave), 0, s, a);
     }
+    return record_hip(hipGetLastError());
+}
+
+size_t sbe_commit_emit_workspace_size(uint64_t n) {
+    // frame lengths (4 B each), two block-sum arrays of nblk + 1 entries, alignment
+    const uint64_t nblk = (n + oj::kBlock - 1) / oj::kBlock;
+    return (size_t)(4 * n + 16 * (nblk + 1) + 3 * 16);
+}
+
+uint64_t sbe_commit_emit_output_bound(uint64_t n, uint64_t id_bytes, int session) {
+    return n * (SBE_LITE_OVERHEAD(2u) + (session ? SBE_SESSION_HDR_LEN : 0u)) + id_bytes;
+}
+
+int sbe_emit_commit_offsets(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                            const sbe_commit_out* plan, const uint32_t* topic_id, const uint8_t* ident_arena,
+                            const uint32_t* ident_off, uint32_t k, const uint8_t* mask, uint32_t flags,
+                            int session, int64_t leadership_term_id, int64_t cluster_session_id, uint8_t* out,
+                            uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    if (!res || !res->out_off || !res->totals || mis(res->out_off, 7) || mis(res->totals, 7) ||
+        mis(res->emit_idx, 7))
+        return SBE_EINVAL;
+    if (k == 0 || k > SBE_COMMIT_MAX_TOPICS || (flags & ~SBE_CE_LAST_ONLY) || ((flags & SBE_CE_LAST_ONLY) && mask) ||
+        (session != 0 && session != 1) || (!out && out_capacity) || n >= (1ull << 32))
+        return SBE_EINVAL;
+    if (n == 0) {
+        if (const int rc = record_hip(hipMemsetAsync(res->out_off, 0, 8, s))) return rc;
+        return record_hip(hipMemsetAsync(res->totals, 0, 24, s));
+    }
+    if (!in || !rec_off || !dec || !dec->status || !dec->flags || !dec->view_off || !dec->view_len || !plan ||
+        !plan->cm || !plan->topic_idx || ((flags & SBE_CE_LAST_ONLY) && !plan->last) || !topic_id || !ident_arena ||
+        !ident_off || !res->status || !workspace)
+        return SBE_EINVAL;
+    if (mis(rec_off, 7) || mis(dec->view_off, 3) || mis(dec->view_len, 3) || mis(dec->seq, 7) ||
+        mis(plan->topic_idx, 3) || ((flags & SBE_CE_LAST_ONLY) && mis(plan->last, 7)) || mis(topic_id, 3) ||
+        mis(ident_off, 3) || mis(workspace, 15))
+        return SBE_EINVAL;
+    if (workspace_bytes < sbe_commit_emit_workspace_size(n)) return SBE_ENOSPC;
+    const uint64_t nblk = (n + oj::kBlock - 1) / oj::kBlock;
+    auto al = [](uintptr_t x) { return (x + 15) & ~(uintptr_t)15; };
+    uintptr_t w = reinterpret_cast<uintptr_t>(workspace);
+    ce::CeArgs a{};
+    a.c = CeIn{in,          rec_off,   dec->status, dec->flags, dec->view_off, dec->view_len,
+               dec->seq,    plan->cm,  plan->topic_idx, plan->last, topic_id,  ident_arena,
+               ident_off,   k,         mask,        flags,      (uint32_t)session, leadership_term_id,
+               cluster_session_id};
+    a.n = n;
+    a.out = out;
+    a.cap = out_capacity;
+    a.out_off = res->out_off;
+    a.status = res->status;
+    a.emit_idx = res->emit_idx;
+    a.totals = res->totals;
+    a.sz = reinterpret_cast<uint32_t*>(w);
+    w = al(w + 4 * n);
+    a.blk_bytes = reinterpret_cast<uint64_t*>(w);
+    a.blk_cnt = a.blk_bytes + (nblk + 1);  // contiguous: one scan runs over both
+    hipLaunchKernelGGL(ce::commit_emit_measure, dim3((uint32_t)nblk), dim3(oj::kBlock), 0, s, a);
+    hipLaunchKernelGGL(oj::order_json_scan_blocks, dim3(1), dim3(oj::kScanThreads), 0, s, a.blk_bytes, 2 * (nblk + 1));
+    hipLaunchKernelGGL(ce::commit_emit_write, dim3((uint32_t)((n + oj::kWWave - 1) / oj::kWWave)), dim3(oj::kWWave),
+                       0, s, a);
     return record_hip(hipGetLastError());
 }
 

@@ -1799,7 +1799,18 @@ const std::string& AutoCommitter::message_identifier(const std::string& topic) c
     return it == identifiers_.end() ? client_id_ : it->second;
 }
 
-CommitPlan AutoCommitter::classify(const ParsedBatch& batch) const {
+// What commit_and_send_batch asks of run() beyond the plan, and what it gets back.
+struct AutoCommitter::EmitRequest {
+    const CommitSendOptions* options;
+    const std::vector<bool>* callback_ok;
+    std::vector<std::uint8_t> status;    // [n] SBE_CE_*
+    std::vector<std::uint64_t> out_off;  // [n + 1]
+    std::vector<std::uint8_t> frames;    // out_off[n] bytes
+};
+
+CommitPlan AutoCommitter::classify(const ParsedBatch& batch) const { return run(batch, nullptr); }
+
+CommitPlan AutoCommitter::run(const ParsedBatch& batch, EmitRequest* emit) const {
     const size_t n = batch.n_;
     CommitPlan plan;
     plan.table.push_back(fallback_);
@@ -1813,13 +1824,23 @@ CommitPlan AutoCommitter::classify(const ParsedBatch& batch) const {
     plan.topic_idx.resize(n);
     plan.last.assign(k, ~0ull);
     plan.count.assign(k + 2, 0);
+    if (emit) {
+        emit->status.assign(n, SBE_CE_NONE);
+        emit->out_off.assign(n + 1, 0);
+        emit->frames.clear();
+    }
     if (n == 0) return plan;
     const Descriptors& d = *batch.desc_;
     const uint64_t lo = batch.rec_off_[0], bytes = batch.rec_off_[n] - lo;
     // staged inputs: offsets (rebased), status, flags, view offsets and lengths, the table, the records
     const size_t o_st = al16((n + 1) * 8), o_fl = o_st + al16(n), o_vo = o_fl + al16(n), o_vl = o_vo + al16(20 * n),
                  o_ta = o_vl + al16(20 * n), o_to = o_ta + SBE_COMMIT_TABLE_BYTES,
-                 o_data = o_to + al16(4 * (SBE_COMMIT_MAX_TOPICS + 1)), stage = o_data + (size_t)bytes + 16;
+                 o_tid = o_to + al16(4 * (SBE_COMMIT_MAX_TOPICS + 1)),
+                 // emit only: topic ids, the identifier table, sequence numbers, the callback mask
+                 o_ia = o_tid + (emit ? al16(4 * SBE_COMMIT_MAX_TOPICS) : 0),
+                 o_io = o_ia + (emit ? SBE_COMMIT_TABLE_BYTES : 0),
+                 o_seq = o_io + (emit ? al16(4 * (SBE_COMMIT_MAX_TOPICS + 1)) : 0), o_mask = o_seq + (emit ? al16(8 * n) : 0),
+                 o_data = o_mask + (emit ? al16(n) : 0), stage = o_data + (size_t)bytes + 16;
     Ctx& c = ctx();
     Pipeline::Slot& s = c.pipe.slot[0];  // serial use of the pipeline's first slot (idle between calls)
     hipStream_t stream = c.batch_stream();
@@ -1845,6 +1866,30 @@ CommitPlan AutoCommitter::classify(const ParsedBatch& batch) const {
         std::memcpy(hp + o_ta + to[j], plan.table[j].data(), plan.table[j].size());
         to[j + 1] = to[j] + (uint32_t)plan.table[j].size();
     }
+    const bool masked = emit && emit->callback_ok;
+    size_t ident_max = 0;
+    if (emit) {  // topic_to_id and message_identifier of every table entry
+        uint32_t* tid = reinterpret_cast<uint32_t*>(hp + o_tid);
+        uint32_t* io = reinterpret_cast<uint32_t*>(hp + o_io);
+        std::memset(hp + o_ia, 0, SBE_COMMIT_TABLE_BYTES);
+        io[0] = 0;
+        for (uint32_t j = 0; j < k; ++j) {
+            const std::string& id = message_identifier(plan.table[j]);
+            if (io[j] + id.size() > SBE_COMMIT_TABLE_BYTES)
+                throw std::length_error("AutoCommitter: the identifier table holds 4096 bytes");
+            tid[j] = CommitManager::topic_to_id(plan.table[j]);
+            std::memcpy(hp + o_ia + io[j], id.data(), id.size());
+            io[j + 1] = io[j] + (uint32_t)id.size();
+            ident_max = std::max(ident_max, id.size());
+        }
+        uint64_t* sq = reinterpret_cast<uint64_t*>(hp + o_seq);
+        for_ranges(n, 4096, [&](size_t x, size_t y) {
+            for (size_t i = x; i < y; ++i) {
+                sq[i] = d.seq(i);
+                if (masked) hp[o_mask + i] = (*emit->callback_ok)[i] ? 1 : 0;
+            }
+        });
+    }
     if (bytes)
         for_ranges((size_t)bytes, size_t(1) << 18, [&](size_t x, size_t y) {
             std::memcpy(hp + o_data + x, batch.data_ + lo + x, y - x);
@@ -1853,7 +1898,13 @@ CommitPlan AutoCommitter::classify(const ParsedBatch& batch) const {
     const size_t p_src = al16(n), p_kind = p_src + al16(n), p_off = p_kind + al16(n), p_len = p_off + al16(4 * n),
                  p_idx = p_len + al16(4 * n), p_last = p_idx + al16(4 * n), p_cnt = p_last + 8 * SBE_COMMIT_MAX_TOPICS,
                  outb = p_cnt + 8 * (SBE_COMMIT_MAX_TOPICS + 2);
-    s.d_out.need(outb);
+    // emit only: status, offsets, totals, the workspace and the frames
+    const int framed = emit && emit->options->session_frame ? 1 : 0;
+    const size_t wsb = emit ? sbe_commit_emit_workspace_size(n) : 0,
+                 bound = emit ? (size_t)sbe_commit_emit_output_bound(n, bytes + n * ident_max, framed) : 0,
+                 p_est = outb, p_eoff = p_est + al16(n), p_tot = p_eoff + al16(8 * (n + 1)), p_ws = p_tot + 32,
+                 p_frames = p_ws + al16(wsb);
+    s.d_out.need(emit ? p_frames + bound : outb);
     hip_check(hipMemcpyAsync(s.d_in.p, hp, stage, hipMemcpyHostToDevice, stream), "H2D");
     uint8_t* di = s.d_in.b();
     uint8_t* dq = s.d_out.b();
@@ -1872,6 +1923,21 @@ CommitPlan AutoCommitter::classify(const ParsedBatch& batch) const {
         c.abort_all();
         fail("sbe_classify_commits");
     }
+    if (emit) {  // the plan is read where classify wrote it
+        const sbe_decoded dec_seq{dec.status, dec.flags, nullptr, nullptr, dec.view_off, dec.view_len,
+                                  reinterpret_cast<uint64_t*>(di + o_seq)};
+        const sbe_commit_emit_out res{reinterpret_cast<uint64_t*>(dq + p_eoff), dq + p_est, nullptr,
+                                      reinterpret_cast<uint64_t*>(dq + p_tot)};
+        if (sbe_emit_commit_offsets(di + o_data, reinterpret_cast<const uint64_t*>(di), n, &dec_seq, &out,
+                                    reinterpret_cast<const uint32_t*>(di + o_tid), di + o_ia,
+                                    reinterpret_cast<const uint32_t*>(di + o_io), k, masked ? di + o_mask : nullptr,
+                                    emit->options->last_only ? SBE_CE_LAST_ONLY : 0u, framed,
+                                    emit->options->leadership_term_id, emit->options->cluster_session_id,
+                                    dq + p_frames, bound, &res, dq + p_ws, wsb, stream) != SBE_OK) {
+            c.abort_all();
+            fail("sbe_emit_commit_offsets");
+        }
+    }
     auto back = [&](void* dst, size_t off, size_t len) {
         hip_check(hipMemcpyAsync(dst, dq + off, len, hipMemcpyDeviceToHost, stream), "D2H");
     };
@@ -1883,7 +1949,16 @@ CommitPlan AutoCommitter::classify(const ParsedBatch& batch) const {
     back(plan.topic_idx.data(), p_idx, 4 * n);
     back(plan.last.data(), p_last, 8 * k);
     back(plan.count.data(), p_cnt, 8 * (k + 2));
+    if (emit) {
+        back(emit->status.data(), p_est, n);
+        back(emit->out_off.data(), p_eoff, 8 * (n + 1));
+    }
     hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    if (emit && emit->out_off[n]) {  // the bound holds every frame: none overflowed
+        emit->frames.resize((size_t)emit->out_off[n]);
+        back(emit->frames.data(), p_frames, emit->frames.size());
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    }
     return plan;
 }
 
@@ -1940,6 +2015,60 @@ std::size_t AutoCommitter::commit_batch(const ParsedBatch& batch, const CommitPl
 std::size_t AutoCommitter::commit_batch(const ParsedBatch& batch, CommitManager& commits,
                                         const std::vector<bool>* callback_ok) const {
     return commit_batch(batch, classify(batch), commits, callback_ok);
+}
+
+CommitSendResult AutoCommitter::commit_and_send_batch(const ParsedBatch& batch, CommitManager& commits,
+                                                      const OfferFn& offer, const CommitSendOptions& options,
+                                                      const std::vector<bool>* callback_ok) const {
+    if (callback_ok && callback_ok->size() != batch.size())
+        throw std::invalid_argument("AutoCommitter: one callback result per record");
+    if (callback_ok && options.last_only)
+        throw std::invalid_argument("AutoCommitter: last_only sends what an unmasked commit_batch commits");
+    EmitRequest emit{&options, callback_ok, {}, {}, {}};
+    const CommitPlan plan = run(batch, &emit);
+    CommitSendResult r;
+    r.commits = commit_batch(batch, plan, commits, callback_ok);
+    std::vector<std::uint8_t> frame;
+    auto send = [&](const std::uint8_t* p, std::size_t len) {
+        ++r.offered;
+        if (offer(p, len)) ++r.accepted;
+    };
+    for (std::size_t i = 0; i < batch.size(); ++i) {
+        const std::uint8_t st = emit.status[i];
+        if (st == SBE_CE_EMITTED) {
+            send(emit.frames.data() + emit.out_off[i], (std::size_t)(emit.out_off[i + 1] - emit.out_off[i]));
+        } else if (st == SBE_CE_E109_MESSAGE_ID) {
+            r.too_long.push_back(i);
+        } else if (st == SBE_CE_HOST) {
+            const bool entry = plan.topic_idx[i] < plan.table.size();  // a table entry whose topic has id 0
+            if (options.last_only && entry && plan.last[plan.topic_idx[i]] != i) continue;
+            const std::string t = entry ? plan.table[plan.topic_idx[i]] : topic(batch, plan, i);
+            if (CommitManager::topic_to_id(t) == 0) {
+                r.unsent.push_back(i);
+                continue;
+            }
+            const std::string_view id = batch.view(i, 2);
+            if (id.size() > SBE_VAR_MAX_LEN) {
+                r.too_long.push_back(i);
+                continue;
+            }
+            const CommitOffset off{t, message_identifier(t), std::string(id), (std::uint64_t)batch.timestamp(i),
+                                   batch.sequence_number(i)};
+            const std::vector<std::uint8_t> rec = commits.build_commit_offset_message(t, client_id_, off);
+            frame.clear();
+            if (options.session_frame) {  // SessionMessageHeader (src/session_manager.cpp:936-967)
+                const std::uint16_t h[4] = {SBE_SESSION_BLOCK_LEN, SBE_SESSION_TEMPLATE_ID, SBE_CLUSTER_SCHEMA_ID,
+                                            SBE_CLUSTER_SCHEMA_VERSION};
+                const std::int64_t ids[3] = {options.leadership_term_id, options.cluster_session_id, 0};
+                frame.resize(SBE_SESSION_HDR_LEN);
+                std::memcpy(frame.data(), h, 8);  // little-endian host, as the rest of the mirror
+                std::memcpy(frame.data() + 8, ids, 24);
+            }
+            frame.insert(frame.end(), rec.begin(), rec.end());
+            send(frame.data(), frame.size());
+        }
+    }
+    return r;
 }
 
 OrderJsonBatch orders_to_json(const std::vector<Order>& orders, const std::vector<std::string>& message_ids) {

@@ -542,6 +542,22 @@ struct CommitPlan {
     std::vector<std::string> table;          // the topic table the plan was made with (entry 0: fallback)
 };
 
+// AutoCommitter::commit_and_send_batch: the session ids of the frames' SessionMessageHeader
+// (send_combined_message, src/cluster_client.cpp:678-682), and what it did.
+struct CommitSendOptions {
+    std::int64_t leadership_term_id = 0;
+    std::int64_t cluster_session_id = 0;
+    bool session_frame = true;  // false: the bare CommitOffsetLite records
+    bool last_only = false;     // one frame per topic-table entry (SBE_CE_LAST_ONLY)
+};
+struct CommitSendResult {
+    std::size_t commits = 0;            // commit_message calls made (commit_batch's return value)
+    std::size_t offered = 0;            // frames handed to the sink
+    std::size_t accepted = 0;           // of those, the ones the sink returned true for
+    std::vector<std::size_t> unsent;    // committed records whose topic has id 0, ascending
+    std::vector<std::size_t> too_long;  // committed records whose message_id exceeds 65534 bytes
+};
+
 // The commit branch of ClusterClient::handle_incoming_message (src/cluster_client.cpp:1251-1288)
 // for a whole ParsedBatch: which records commit, and under which topic, is decided on the device
 // (sbe_classify_commits: should_skip_auto_commit :847-886 and extract_topic_from_message :756-806
@@ -575,8 +591,28 @@ public:
     // The reference's sequence: every committable record, in order.
     std::size_t commit_record_by_record(const ParsedBatch& batch, const CommitPlan& plan, CommitManager& commits,
                                         const std::vector<bool>* callback_ok = nullptr) const;
+    // Both halves of ClusterClient::commit_message (src/cluster_client.cpp:626-633) for the batch:
+    // the commits go into `commits` exactly as commit_batch makes them, and for every committed
+    // record the frame send_commit_offset sends (:1264-1278, a CommitOffsetLite behind the session
+    // header) goes to `offer`, in record order.  One staged upload; sbe_classify_commits and
+    // sbe_emit_commit_offsets run back to back on the stream (the plan stays on the device between
+    // them); the plan and the emit result come back in one download, the frames, whose size the
+    // emit result gives, in the copy after it.  A record whose topic the device table does not
+    // resolve (SBE_CE_HOST) is resolved here: with a non-zero topic_to_id its frame is built by
+    // build_commit_offset_message and offered at its place; with topic id 0 (the reference's JSON
+    // fallback, not built) its index goes to `unsent`, and nothing throws.  A message_id over
+    // 65534 bytes (the reference throws E109) goes to `too_long`.
+    // last_only: only the last committable record of every table entry is sent (what commit_batch
+    // commits without a mask); std::invalid_argument together with callback_ok.
+    // std::length_error when the identifiers of the table exceed 4096 bytes.
+    CommitSendResult commit_and_send_batch(const ParsedBatch& batch, CommitManager& commits, const OfferFn& offer,
+                                           const CommitSendOptions& options = {},
+                                           const std::vector<bool>* callback_ok = nullptr) const;
 
 private:
+    struct EmitRequest;
+    // classify(), and with `emit` the emit call behind it on the same staged inputs
+    CommitPlan run(const ParsedBatch& batch, EmitRequest* emit) const;
     std::string client_id_, fallback_;
     std::map<std::string, std::string> identifiers_;
 };

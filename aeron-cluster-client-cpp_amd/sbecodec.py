@@ -15,6 +15,8 @@ Reference surface mirrored (paths relative to the reference tree):
   decode_batch(PARSE) ~ MessageParser::parse_message        src/sbe_encoder.cpp:513-551
   classify_commits    ~ handle_incoming_message's commit decision src/cluster_client.cpp:1198-1303
                         (should_skip_auto_commit :847-886, extract_topic_from_message :756-806)
+  emit_commit_offsets ~ commit_message's send_commit_offset src/cluster_client.cpp:626-633, :1264-1278
+                        (CommitOffsetLite src/commit_manager.cpp:107-132 behind the session header)
   decode_batch(EGRESS)~ decode_ack + MessageHandler::on_egress
                         src/ack_decoder.cpp:29-105, include/aeron_cluster/message_handler.hpp:35-68
   order_to_json_batch ~ Order::to_json src/order_types.cpp:122-181 and publish_order's headers JSON
@@ -111,6 +113,11 @@ class _CommitOut(ctypes.Structure):
                 ("last", ctypes.c_void_p), ("count", ctypes.c_void_p)]
 
 
+class _CommitEmitOut(ctypes.Structure):
+    _fields_ = [("out_off", ctypes.c_void_p), ("status", ctypes.c_void_p), ("emit_idx", ctypes.c_void_p),
+                ("totals", ctypes.c_void_p)]
+
+
 class _AckOut(ctypes.Structure):
     _fields_ = [("code", ctypes.c_void_p), ("base_ns", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
 
@@ -180,6 +187,17 @@ def _load():
                                          ctypes.POINTER(_Decoded), ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_uint32, ctypes.POINTER(_CommitOut), ctypes.c_void_p,
                                          ctypes.c_size_t, ctypes.c_void_p]
+    if hasattr(lib, "sbe_emit_commit_offsets"):
+        lib.sbe_commit_emit_workspace_size.restype = ctypes.c_size_t
+        lib.sbe_commit_emit_workspace_size.argtypes = [ctypes.c_uint64]
+        lib.sbe_commit_emit_output_bound.restype = ctypes.c_uint64
+        lib.sbe_commit_emit_output_bound.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
+        lib.sbe_emit_commit_offsets.restype = ctypes.c_int
+        lib.sbe_emit_commit_offsets.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_Decoded), ctypes.POINTER(_CommitOut),
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+            ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(_CommitEmitOut), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.sbe_inflight_table_size.restype = ctypes.c_size_t
     lib.sbe_inflight_table_size.argtypes = [ctypes.c_uint64]
     lib.sbe_inflight_workspace_size.restype = ctypes.c_size_t
@@ -625,6 +643,115 @@ def classify_commits(data, rec_off, dec: Decoded, topics, out: CommitPlan | None
     if n < out.cm.numel():
         out = CommitPlan(*(getattr(out, f)[:n] for f, _ in _COMMIT_KEYS[:6]), out.last, out.count)
     return out
+
+
+# sbe_emit_commit_offsets: per-record status and the flag (include/sbecodec.h)
+CE_NONE, CE_EMITTED, CE_HOST, CE_E109_MESSAGE_ID, CE_OVERFLOW = range(5)
+CE_LAST_ONLY = 0x1
+
+
+@dataclass
+class CommitFrames:
+    out: torch.Tensor | None  # u8 frames, record i = out[out_off[i]:out_off[i+1]]; None for a sizing call
+    out_off: torch.Tensor     # i64 [n+1] the full layout, whatever the capacity
+    status: torch.Tensor      # u8 [n] CE_*
+    emit_idx: torch.Tensor    # i64 [n] (u64): the first totals[0] entries are the records with a frame
+    totals: torch.Tensor      # i64 [3] (u64): records with a frame, their bytes, CE_HOST records
+    workspace: torch.Tensor | None = None
+
+    def numpy(self):
+        import numpy as np
+        d = {k: getattr(self, k).cpu().numpy().view(t) for k, t in
+             (("out_off", np.uint64), ("status", np.uint8), ("emit_idx", np.uint64), ("totals", np.uint64))}
+        d["emit_idx"] = d["emit_idx"][: int(d["totals"][0])]
+        d["out"] = None if self.out is None else self.out.cpu().numpy()
+        return d
+
+
+def commit_identifier_table(identifiers, device):
+    """The device messageIdentifier table of emit_commit_offsets, one entry per topic-table entry
+    (CommitManager::message_identifier of that topic): (arena uint8 [COMMIT_TABLE_BYTES], off int32 [k+1])."""
+    return commit_topic_table(identifiers, device)
+
+
+def commit_emit_workspace_size(n: int) -> int:
+    return int(lib().sbe_commit_emit_workspace_size(n))
+
+
+def commit_emit_output_bound(n: int, id_bytes: int, session: bool = True) -> int:
+    return int(lib().sbe_commit_emit_output_bound(n, id_bytes, 1 if session else 0))
+
+
+def emit_commit_offsets(data, rec_off, dec: Decoded, plan: CommitPlan, topic_ids, identifiers, mask=None, flags=0,
+                        session=True, leadership_term_id=0, cluster_session_id=0, out=None, out_capacity=None,
+                        out_off=None, status=None, emit_idx=None, totals=None, workspace=None,
+                        stream=None) -> CommitFrames:
+    """The CommitOffsetLite frame of every record classify_commits committed, compacted in record
+    order on the device (send_commit_offset, src/cluster_client.cpp:1264-1278): `plan` is
+    classify_commits' result for the same data / rec_off / dec and a table of k entries.
+    topic_ids: int32 [k] device tensor (u32, 0 = unknown) or a list of ints; identifiers: a list of
+    bytes or the (arena, off) pair commit_identifier_table made; mask: uint8 [n] callback_ok or
+    None; flags: 0 or CE_LAST_ONLY.  dec.seq (or None) gives the frames' sequence.
+    out: a uint8 device tensor (no alignment needed); out_capacity = 0 without `out` only sizes
+    (out_off / totals hold the full layout).  With neither, `out` is allocated at the bound
+    n * (24 [+ 32]) + the records' bytes + n * the longest identifier, which reads the identifier
+    offsets back once when `identifiers` is a device pair."""
+    data = _dev(data, torch.uint8, "data")
+    rec_off = _dev(rec_off, torch.int64, "rec_off")
+    n = int(rec_off.numel()) - 1
+    dev = data.device
+    if data.numel() == 0:
+        data = torch.zeros(16, dtype=torch.uint8, device=dev)
+    if isinstance(topic_ids, torch.Tensor):
+        topic_ids = _dev(topic_ids, torch.int32, "topic_ids")
+    else:
+        import numpy as np
+        topic_ids = torch.from_numpy(np.asarray(list(topic_ids), np.uint32).view(np.int32)).to(dev)
+    k = int(topic_ids.numel())
+    arena, off = identifiers if isinstance(identifiers, tuple) else commit_identifier_table(identifiers, dev)
+    arena = _dev(arena, torch.uint8, "identifier arena")
+    off = _dev(off, torch.int32, "identifier offsets")
+    if arena.numel() < COMMIT_TABLE_BYTES:
+        raise SbeError(f"the identifier arena must hold {COMMIT_TABLE_BYTES} bytes")
+    if off.numel() != k + 1:
+        raise SbeError("identifiers and topic_ids must have one entry per topic-table entry")
+    mask = _dev(mask, torch.uint8, "mask")
+    if mask is not None and mask.numel() < n:
+        raise SbeError("mask is shorter than the batch")
+    if out is None and out_capacity is None:
+        if isinstance(identifiers, tuple):
+            o = off.cpu()
+            longest = int((o[1:] - o[:-1]).clamp(min=0).max().item()) if k else 0
+        else:
+            longest = max((len(bytes(t)) for t in identifiers), default=0)
+        out_capacity = commit_emit_output_bound(n, int(data.numel()) + n * min(longest, COMMIT_TABLE_BYTES), session)
+    if out is None and out_capacity:
+        out = torch.empty(int(out_capacity), dtype=torch.uint8, device=dev)
+    out = _dev(out, torch.uint8, "out")
+    cap = 0 if out is None else int(out.numel()) if out_capacity is None else int(out_capacity)
+    if out is not None and cap > out.numel():
+        raise SbeError(f"out_capacity {cap} exceeds the out tensor ({out.numel()} bytes)")
+    m = max(n, 1)
+    out_off = torch.empty(n + 1, dtype=torch.int64, device=dev) if out_off is None else _dev(out_off, torch.int64, "out_off")
+    status = torch.empty(m, dtype=torch.uint8, device=dev) if status is None else _dev(status, torch.uint8, "status")
+    emit_idx = torch.empty(m, dtype=torch.int64, device=dev) if emit_idx is None else _dev(emit_idx, torch.int64, "emit_idx")
+    totals = torch.empty(3, dtype=torch.int64, device=dev) if totals is None else _dev(totals, torch.int64, "totals")
+    if out_off.numel() < n + 1 or status.numel() < n or emit_idx.numel() < n or totals.numel() < 3:
+        raise SbeError("out_off / status / emit_idx / totals are shorter than the batch")
+    need = commit_emit_workspace_size(n)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    d = _Decoded(*(getattr(dec, f).data_ptr() for f in ("status", "flags", "hdr", "ts", "view_off", "view_len")),
+                 None if dec.seq is None else _dev(dec.seq, torch.int64, "dec.seq").data_ptr())
+    p = _CommitOut(*(getattr(plan, f).data_ptr() for f, _ in _COMMIT_KEYS))
+    r = _CommitEmitOut(out_off.data_ptr(), status.data_ptr(), emit_idx.data_ptr(), totals.data_ptr())
+    rc = lib().sbe_emit_commit_offsets(_ptr(data), _ptr(rec_off), n, ctypes.byref(d), ctypes.byref(p),
+                                       _ptr(topic_ids), _ptr(arena), _ptr(off), k, _ptr(mask), int(flags),
+                                       1 if session else 0, int(leadership_term_id), int(cluster_session_id),
+                                       _ptr(out), cap, ctypes.byref(r), _ptr(workspace), workspace.numel(),
+                                       _stream(stream))
+    _check(rc, "sbe_emit_commit_offsets")
+    return CommitFrames(out, out_off[: n + 1], status[:n], emit_idx[:n], totals[:3], workspace)
 
 
 # sbe_inflight_*: ack correlation (include/sbecodec.h)

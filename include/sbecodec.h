@@ -49,6 +49,10 @@
  *                                  extract_topic_from_message :756-806, and the last commit per
  *                                  topic that CommitManager::commit_message keeps
  *                                  (src/commit_manager.cpp:29-35)
+ * sbe_emit_commit_offsets()       the other half of commit_message src/cluster_client.cpp:626-633:
+ *                                  send_commit_offset :1264-1278, i.e. build_commit_offset_message
+ *                                  src/commit_manager.cpp:107-132 behind send_combined_message's session
+ *                                  header :678-682, for the records sbe_classify_commits committed
  * sbe_decode_batch(ON_EGRESS)     decode_ack  src/ack_decoder.cpp:29-105 (AckInfo
  *                                  include/aeron_cluster/ack_decoder.hpp:9-15) and
  *                                  MessageHandler::on_egress include/aeron_cluster/message_handler.hpp:35-68
@@ -404,6 +408,69 @@ size_t sbe_commit_workspace_size(uint64_t n, uint32_t k);
 int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
                          const uint8_t* topic_arena, const uint32_t* topic_off, uint32_t k,
                          const sbe_commit_out* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ============================== commit-offset frames ============================== */
+/* The second half of ClusterClient::commit_message (src/cluster_client.cpp:626-633) for a batch
+ * that sbe_decode_batch(SBE_DEC_PARSE_MESSAGE) and sbe_classify_commits have been over, with no
+ * host round trip between them: for every committed record the frame send_commit_offset sends
+ * (:1264-1278), compacted in record order.  A frame is
+ *   [the 32-B SessionMessageHeader {24,1,111,8, termId, sessionId, 0} when `session`]
+ *   header {12,301,1,1}, u32 topicId, u64 sequence, u16 + messageId, u16 + messageIdentifier
+ * (CommitManager::build_commit_offset_message, src/commit_manager.cpp:107-132, behind
+ * send_combined_message :678-682): topicId = topic_id[topic_idx[i]], messageId = view 2 of record
+ * i (ParseResult.message_id), messageIdentifier = entry topic_idx[i] of the identifier table,
+ * sequence = dec->seq[i] when dec->status[i] == SBE_ST_TM and dec->flags[i] has SBE_FL_SEQ_KEY or
+ * SBE_FL_SEQ_ESC, else 0 (decode writes no other entry; dec->seq == NULL: 0 everywhere).
+ * status[i], the first line that applies: */
+#define SBE_CE_NONE 0u            /* plan->cm[i] != SBE_CM_COMMIT, or mask[i] == 0 (the callback failed); under
+                                     SBE_CE_LAST_ONLY also a table-entry record that is not its entry's last */
+#define SBE_CE_EMITTED 1u         /* the frame is out[out_off[i] .. out_off[i+1]) */
+#define SBE_CE_HOST 2u            /* topic_idx[i] >= k (SBE_TOPIC_UNKNOWN, SBE_TOPIC_HOST) or topic_id of the
+                                     entry is 0: the host resolves the topic, or owes the reference's JSON
+                                     fallback (src/commit_manager.cpp:134-175, not built); 0 bytes */
+#define SBE_CE_E109_MESSAGE_ID 3u /* messageId over 65534 bytes: computeLength throws [E109]; 0 bytes */
+#define SBE_CE_OVERFLOW 4u        /* the frame ends past out_capacity: not written, and no byte of out from the
+                                     end of the last frame that fits is touched */
+#define SBE_CE_LAST_ONLY 0x1u     /* flag: emit only record plan->last[topic_idx[i]] of each table entry, at most
+                                     k frames (the once-per-entry shortcut of a batch commit; no reference
+                                     counterpart; SBE_EINVAL together with a mask).  SBE_CE_HOST records are
+                                     reported as without the flag */
+
+/* out_off / totals always describe the full layout, whatever out_capacity is (SBE_CE_OVERFLOW
+ * records keep their length), so a call with out = NULL, out_capacity = 0 sizes a batch. */
+typedef struct sbe_commit_emit_out {
+    uint64_t* out_off;  /* [n + 1] record order; a record without a frame has length 0 */
+    uint8_t* status;    /* [n] SBE_CE_* */
+    uint64_t* emit_idx; /* [n] or NULL: the first totals[0] entries are written, the indices of the records
+                           with a frame (EMITTED or OVERFLOW), ascending */
+    uint64_t* totals;   /* [3] records with a frame, their bytes (= out_off[n]), SBE_CE_HOST records */
+} sbe_commit_emit_out;
+
+/* Bytes of device workspace for n records (frame lengths and block sums only, no text). */
+size_t sbe_commit_emit_workspace_size(uint64_t n);
+/* Upper bound of the frames of n emitting records whose messageIds and messageIdentifiers total
+ * id_bytes (the ids lie inside the records: rec_off[n] - rec_off[0] bounds their part). */
+uint64_t sbe_commit_emit_output_bound(uint64_t n, uint64_t id_bytes, int session);
+
+/* in / rec_off / dec: the arguments and outputs of the decode call; plan: what sbe_classify_commits
+ * wrote for them with a table of k entries (cm, topic_idx; last under SBE_CE_LAST_ONLY).
+ * topic_id [k]: CommitManager::topic_to_id of entry j, 0 = unknown.  The identifier table is laid
+ * out and clamped as the topic table is: entry j = ident_arena[ident_off[j] .. ident_off[j+1]),
+ * ident_arena readable for SBE_COMMIT_TABLE_BYTES, offsets clamped to that, a reversed entry empty;
+ * the host does not read ident_off.  mask: [n] u8 callback_ok, or NULL = all.
+ * Alignment: u32 arrays 4 B, u64 arrays 8 B, workspace 16 B; out needs none.  n < 2^32.
+ * n == 0 is SBE_OK with out_off[0] = 0 and totals zeroed (only res, out_off, totals, k, flags and
+ * session are looked at).  SBE_EINVAL (nothing written): a null pointer where n > 0, k == 0 or
+ * k > SBE_COMMIT_MAX_TOPICS, a misaligned array, unknown flag bits, SBE_CE_LAST_ONLY with a mask,
+ * session not 0 / 1, out NULL with a capacity; SBE_ENOSPC: workspace too small.
+ * On `stream`: the sizing launch, one scan launch over its block sums, the writing launch.  No atomics:
+ * a repeated call writes identical results. */
+int sbe_emit_commit_offsets(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                            const sbe_commit_out* plan, const uint32_t* topic_id, const uint8_t* ident_arena,
+                            const uint32_t* ident_off, uint32_t k, const uint8_t* mask, uint32_t flags,
+                            int session, int64_t leadership_term_id, int64_t cluster_session_id, uint8_t* out,
+                            uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* ================================= ack correlation ================================= */
 /* The step of the client's message loop that joins the two directions: publish_topic remembers

@@ -14,6 +14,9 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
                          BEGIN/END reassembly (all its launches, torch events around the call)
   materialize            1 M fixed-256 records' parse_message views copied into one arena
                          (sbe_materialize_views, all its launches, torch events around the call)
+  commit_emit            1 M decoded and classified fixed-256 Orders, all committed → session-framed
+                         CommitOffsetLite frames in one fused call (sbe_emit_commit_offsets), and in the
+                         same run sbe_encode_lite_batch on a pre-gathered arena of the same ids
   ack_correlate          1 M "pub_<nanos>" uuids remembered in a 2 M-slot in-flight table, then 1 M full
                          acks (about 10 % unknown ids, 1 % repeated ids) decoded on-egress and matched;
                          remember, match and the decode of the same ack batch timed in the same run, and
@@ -502,6 +505,87 @@ def row_autocommit(steps, warmup):
         torch.cuda.empty_cache()
 
 
+def row_commit_emit(steps, warmup):
+    """sbe_emit_commit_offsets over 1 M decoded and classified fixed-256 Orders whose headers all
+    carry a known topic (every record emits a session-framed CommitOffsetLite; short identifiers),
+    and, in the same run, the device part of the chain it replaces: sbe_encode_lite_batch (301) on
+    a pre-gathered arena of the same ids and identifiers.  The baseline's host gather and its
+    session framing are left out, which favours the baseline.  Bytes of the fused call, per record:
+    rec_off 8, cm 1, topic_idx 4, status + flags 2, view 2 offset and length 8, seq 8 and the id
+    read; out_off 8, status 1, emit_idx 8 and the frame written.  The baseline's: lengths 8,
+    topicId 4, sequence 8 and both strings read; out_off 8, status 1 and the bare record written."""
+    n = 1_000_000
+    arena, L, ts = T.fixed256_orders(n)
+    a2 = arena.reshape(n, 222).copy()
+    a2[:, 190:] = np.frombuffer(b'{"topic":"orders","a":"CREATE"} ', np.uint8)
+    data, off = T.oracle_encode(a2.reshape(-1), L, ts)[:2]
+    topics = [b"orders", b"order_request_topic", b"order_notification_topic"]
+    idents = [b"client-01", b"sub-req", b"sub-ntf"]
+    d0, o0 = dev(data, torch.uint8), dev(np.asarray(off, np.uint64), torch.int64)
+    table = sbecodec.commit_topic_table(topics, "cuda")
+    itab = sbecodec.commit_identifier_table(idents, "cuda")
+    tid = dev(np.array([3, 1, 2], np.uint32), torch.int32)
+    # the baseline's arena, gathered on the host once: id and identifier of every record, back to back
+    Lh = np.asarray(L, np.int64).reshape(n, 5)
+    id_off = np.asarray(off[:-1], np.int64) + 24 + 2 + Lh[:, 0] + 2 + Lh[:, 1] + 2
+    idl = Lh[:, 2]
+    assert int(idl.min()) == int(idl.max())  # fixed-size records: one id length
+    w = int(idl[0])
+    ids = data[(id_off[:, None] + np.arange(w)[None, :]).reshape(-1)].reshape(n, w)
+    g_arena = np.concatenate([ids, np.tile(np.frombuffer(idents[0], np.uint8), (n, 1))], axis=1).reshape(-1)
+    g_len = np.tile(np.array([w, len(idents[0])], np.int32), n)
+    g0 = (dev(g_arena, torch.uint8), dev(g_len, torch.int32), torch.full((n,), 3, dtype=torch.int32, device="cuda"),
+          torch.zeros(n, dtype=torch.int64, device="cuda"))
+
+    def make(k):
+        d, o = d0.clone(), o0.clone()
+        dec = sbecodec.decode_batch(d, o, sbecodec.DEC_PARSE_MESSAGE, out=sbecodec.alloc_decoded(n, "cuda"),
+                                    in_bytes=data.size, seq=True)
+        plan = sbecodec.classify_commits(d, o, dec, table)
+        fr = sbecodec.emit_commit_offsets(d, o, dec, plan, tid, itab, leadership_term_id=7, cluster_session_id=9)
+        g = tuple(x.clone() for x in g0)
+        enc = sbecodec.encode_lite_batch(sbecodec.COMMIT_OFFSET_LITE, *g)
+        return d, o, dec, plan, fr, g, enc
+
+    R = Rot(make)
+    torch.cuda.synchronize()
+    d, o, dec, plan, fr0, _, enc0 = R.sets[0]
+    assert int(fr0.totals[0]) == n and int(fr0.status.min()) == sbecodec.CE_EMITTED
+    bare = sbecodec.emit_commit_offsets(d, o, dec, plan, tid, itab, session=False)
+    torch.cuda.synchronize()
+    total_b = int(enc0.out_off[n])
+    # without the session frame the fused call writes the baseline's stream
+    assert int(bare.totals[1]) == total_b and torch.equal(bare.out[:total_b], enc0.out[:total_b])
+    del bare
+    total = int(fr0.totals[1])
+
+    def fused_fn():
+        d, o, dec, plan, fr, _, _ = R.next()
+        sbecodec.emit_commit_offsets(d, o, dec, plan, tid, itab, leadership_term_id=7, cluster_session_id=9,
+                                     out=fr.out, out_off=fr.out_off, status=fr.status, emit_idx=fr.emit_idx,
+                                     totals=fr.totals, workspace=fr.workspace)
+
+    def base_fn():
+        *_, g, enc = R.next()
+        sbecodec.encode_lite_batch(sbecodec.COMMIT_OFFSET_LITE, *g, out=enc.out, out_off=enc.out_off,
+                                   status=enc.status, workspace=enc.workspace)
+
+    ms_f = _event_ms(fused_fn, steps, warmup)
+    ms_b = _event_ms(base_fn, steps, warmup)
+    ms_f2 = _event_ms(fused_fn, steps, warmup)  # again after the baseline: drift between the two shows here
+    nb_f = n * (8 + 1 + 4 + 2 + 8 + 8 + w) + n * (8 + 1 + 8) + total
+    nb_b = n * (8 + 4 + 8 + w + len(idents[0])) + n * (8 + 1) + total_b
+    if max(ms_f, ms_f2) > ms_b:
+        print(f"WARNING commit_emit: fused {ms_f:.4f} / {ms_f2:.4f} ms is slower than the partial baseline {ms_b:.4f} ms",
+              file=sys.stderr, flush=True)
+    print(json.dumps({"row": "commit_emit", "fused_not_slower_than_partial_baseline": bool(max(ms_f, ms_f2) <= ms_b),
+                      "baseline_over_fused": ms_b / ms_f, "id_bytes": w, "frame_bytes": total // n}), flush=True)
+    line("commit_emit", n, ms_f * 1e-3,
+         {"sbe_emit_commit_offsets (fused, session-framed: all launches)": (ms_f, nb_f),
+          "sbe_emit_commit_offsets (measured again after the baseline)": (ms_f2, nb_f),
+          "baseline: sbe_encode_lite_batch on a pre-gathered arena (no gather, no session frame)": (ms_b, nb_b)})
+
+
 def row_ack_correlate(steps, warmup):
     """sbe_inflight_remember of 1 M publish_topic uuids into an empty 2 M-slot table, then
     sbe_inflight_match_acks of 1 M full acks (T.ack_wire; about 10 % ids nobody sent, 1 % ids that
@@ -595,7 +679,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,ack_correlate")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,commit_emit,ack_correlate")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -624,6 +708,8 @@ def main():
             row_materialize(args.steps, args.warmup)
         elif r == "autocommit":
             row_autocommit(args.steps, args.warmup)
+        elif r == "commit_emit":
+            row_commit_emit(args.steps, args.warmup)
         elif r == "ack_correlate":
             row_ack_correlate(args.steps, args.warmup)
         elif r.startswith("lite"):
