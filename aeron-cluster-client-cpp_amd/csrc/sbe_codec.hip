@@ -4827,6 +4827,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 #include "order_publish.hpp"
 #include "inflight.hpp"
 #include "commit_emit.hpp"
+#include "commit_fallback.hpp"
 
 }  // namespace
 
@@ -5457,14 +5458,33 @@ uint64_t sbe_commit_emit_output_bound(uint64_t n, uint64_t id_bytes, int session
     return n * (SBE_LITE_OVERHEAD(2u) + (session ? SBE_SESSION_HDR_LEN : 0u)) + id_bytes;
 }
 
+uint64_t sbe_commit_fallback_output_bound(uint64_t n, uint64_t id_bytes, int session) {
+    // the larger of two is at most their sum
+    return n * (uint64_t)(SBE_CE_FALLBACK_REC_MAX + SBE_SESSION_HDR_LEN) + sbe_commit_emit_output_bound(n, id_bytes, session);
+}
+
 int sbe_emit_commit_offsets(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
                             const sbe_commit_out* plan, const uint32_t* topic_id, const uint8_t* ident_arena,
                             const uint32_t* ident_off, uint32_t k, const uint8_t* mask, uint32_t flags,
                             int session, int64_t leadership_term_id, int64_t cluster_session_id, uint8_t* out,
                             uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
                             size_t workspace_bytes, void* stream) {
+    return sbe_emit_commit_offsets_ex(in, rec_off, n, dec, plan, topic_id, ident_arena, ident_off, k, mask, flags,
+                                      session, leadership_term_id, cluster_session_id, out, out_capacity, res,
+                                      workspace, workspace_bytes, stream, nullptr);
+}
+
+int sbe_emit_commit_offsets_ex(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                               const sbe_commit_out* plan, const uint32_t* topic_id, const uint8_t* ident_arena,
+                               const uint32_t* ident_off, uint32_t k, const uint8_t* mask, uint32_t flags,
+                               int session, int64_t leadership_term_id, int64_t cluster_session_id, uint8_t* out,
+                               uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
+                               size_t workspace_bytes, void* stream, const sbe_commit_fallback* fb) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    if (fb && (!fb->topic_arena || !fb->topic_off || !fb->default_ident || mis(fb->topic_off, 3) ||
+               fb->default_ident_len > SBE_COMMIT_TABLE_BYTES))
+        return SBE_EINVAL;
     if (!res || !res->out_off || !res->totals || mis(res->out_off, 7) || mis(res->totals, 7) ||
         mis(res->emit_idx, 7))
         return SBE_EINVAL;
@@ -5482,6 +5502,9 @@ int sbe_emit_commit_offsets(const uint8_t* in, const uint64_t* rec_off, uint64_t
     if (mis(rec_off, 7) || mis(dec->view_off, 3) || mis(dec->view_len, 3) || mis(dec->seq, 7) ||
         mis(plan->topic_idx, 3) || ((flags & SBE_CE_LAST_ONLY) && mis(plan->last, 7)) || mis(topic_id, 3) ||
         mis(ident_off, 3) || mis(workspace, 15))
+        return SBE_EINVAL;
+    if (fb && (!dec->ts || !plan->topic_kind || !plan->topic_off || !plan->topic_len || mis(dec->ts, 7) ||
+               mis(plan->topic_off, 3) || mis(plan->topic_len, 3)))
         return SBE_EINVAL;
     if (workspace_bytes < sbe_commit_emit_workspace_size(n)) return SBE_ENOSPC;
     const uint64_t nblk = (n + oj::kBlock - 1) / oj::kBlock;
@@ -5503,10 +5526,21 @@ int sbe_emit_commit_offsets(const uint8_t* in, const uint64_t* rec_off, uint64_t
     w = al(w + 4 * n);
     a.blk_bytes = reinterpret_cast<uint64_t*>(w);
     a.blk_cnt = a.blk_bytes + (nblk + 1);  // contiguous: one scan runs over both
+    const dim3 wgrid((uint32_t)((n + oj::kWWave - 1) / oj::kWWave));
+    if (fb) {
+        cf::CfArgs f{};
+        f.f = CfIn{a.c,           dec->ts,       plan->topic_kind,  plan->topic_off,       plan->topic_len, fb->topic_arena,
+                   fb->topic_off, fb->default_ident, fb->default_ident_len, fb->now_ns, fb->uuid_ns};
+        f.e = a;
+        hipLaunchKernelGGL(cf::commit_fallback_measure, dim3((uint32_t)nblk), dim3(oj::kBlock), 0, s, f);
+        hipLaunchKernelGGL(oj::order_json_scan_blocks, dim3(1), dim3(oj::kScanThreads), 0, s, a.blk_bytes,
+                           2 * (nblk + 1));
+        hipLaunchKernelGGL(cf::commit_fallback_write, wgrid, dim3(oj::kWWave), 0, s, f);
+        return record_hip(hipGetLastError());
+    }
     hipLaunchKernelGGL(ce::commit_emit_measure, dim3((uint32_t)nblk), dim3(oj::kBlock), 0, s, a);
     hipLaunchKernelGGL(oj::order_json_scan_blocks, dim3(1), dim3(oj::kScanThreads), 0, s, a.blk_bytes, 2 * (nblk + 1));
-    hipLaunchKernelGGL(ce::commit_emit_write, dim3((uint32_t)((n + oj::kWWave - 1) / oj::kWWave)), dim3(oj::kWWave),
-                       0, s, a);
+    hipLaunchKernelGGL(ce::commit_emit_write, wgrid, dim3(oj::kWWave), 0, s, a);
     return record_hip(hipGetLastError());
 }
 

@@ -1629,7 +1629,7 @@ EncodedBatch CommitManager::build_commit_offset_batch(const std::vector<CommitOf
         ids[i] = topic_to_id(offsets[i].topic);
         if (ids[i] == 0)
             throw std::runtime_error("sbecodec: commit offset for unknown topic '" + offsets[i].topic +
-                                     "' needs the jsoncpp TopicMessage fallback (not built)");
+                                     "' needs the JSON TopicMessage fallback (build_commit_offset_fallback)");
     }
     EncodePlan plan;
     plan.overhead = SBE_LITE_OVERHEAD(2);
@@ -1665,6 +1665,120 @@ std::vector<std::uint8_t> CommitManager::build_commit_offset_message(const std::
     if (st == 1 || st == 2) throw std::runtime_error(kLiteE109[st - 1]);
     if (st != SBE_ENC_OK) throw std::runtime_error("sbecodec: encode failed");
     return b.bytes.to_vector();
+}
+
+namespace {
+// jsoncpp valueToQuotedStringN(s, emitUTF8 = false), utf8ToCodepoint included (json_writer.cpp):
+// what csrc/order_json.hpp's oj::quoted writes on the device.
+void json_quote(std::string& out, std::string_view s) {
+    auto hex4 = [&](uint32_t v) {
+        static const char hx[] = "0123456789abcdef";
+        out += "\\u";
+        for (int sh = 12; sh >= 0; sh -= 4) out += hx[(v >> sh) & 15];
+    };
+    out += '"';
+    for (size_t i = 0; i < s.size();) {
+        const uint32_t c = (uint8_t)s[i];
+        const size_t left = s.size() - i;
+        auto at = [&](size_t k) { return (uint32_t)(uint8_t)s[i + k]; };
+        switch (c) {
+            case '"': out += "\\\""; ++i; continue;
+            case '\\': out += "\\\\"; ++i; continue;
+            case '\b': out += "\\b"; ++i; continue;
+            case '\f': out += "\\f"; ++i; continue;
+            case '\n': out += "\\n"; ++i; continue;
+            case '\r': out += "\\r"; ++i; continue;
+            case '\t': out += "\\t"; ++i; continue;
+            default: break;
+        }
+        if (c >= 0x20 && c < 0x80) {
+            out += (char)c;
+            ++i;
+            continue;
+        }
+        uint32_t cp = 0xFFFD;
+        size_t used = 1;
+        if (c < 0x20) {
+            cp = c;
+        } else if (c < 0xE0) {
+            if (left >= 2) {
+                cp = ((c & 0x1F) << 6) | (at(1) & 0x3F);
+                used = 2;
+                if (cp < 0x80) cp = 0xFFFD;
+            }
+        } else if (c < 0xF0) {
+            if (left >= 3) {
+                cp = ((c & 0x0F) << 12) | ((at(1) & 0x3F) << 6) | (at(2) & 0x3F);
+                used = 3;
+                if ((cp >= 0xD800 && cp <= 0xDFFF) || cp < 0x800) cp = 0xFFFD;
+            }
+        } else if (c < 0xF8) {
+            if (left >= 4) {
+                cp = ((c & 0x07) << 18) | ((at(1) & 0x3F) << 12) | ((at(2) & 0x3F) << 6) | (at(3) & 0x3F);
+                used = 4;
+                if (cp < 0x10000) cp = 0xFFFD;
+            }
+        }
+        i += used;
+        if (cp < 0x10000) {
+            hex4(cp);
+        } else {
+            cp -= 0x10000;
+            hex4(0xD800 + ((cp >> 10) & 0x3FF));
+            hex4(0xDC00 + (cp & 0x3FF));
+        }
+    }
+    out += '"';
+}
+}  // namespace
+
+std::string CommitManager::serialize_commit_offset(const CommitOffset& offset) {
+    std::string t = "{\"action\":\"COMMIT_OFFSET\",\"messageIdentifier\":";
+    json_quote(t, offset.message_identifier);
+    t += ",\"message_id\":";
+    json_quote(t, offset.message_id);
+    t += ",\"sequence_number\":" + std::to_string(offset.sequence_number);
+    t += ",\"timestamp_nanos\":" + std::to_string(offset.timestamp_nanos);
+    t += ",\"topic\":";
+    json_quote(t, offset.topic);
+    t += '}';
+    return t;
+}
+
+std::vector<std::uint8_t> CommitManager::build_commit_offset_fallback(const std::string& client_id,
+                                                                      const CommitOffset& offset,
+                                                                      const ClockFn& clock) const {
+    auto now = [&] { return clock ? clock() : now_nanos_sys(); };
+    const std::string text = serialize_commit_offset(offset);
+    std::vector<std::uint8_t> buf;
+    buf.reserve(SBE_CE_FALLBACK_REC_MAX);
+    auto put16 = [&](uint32_t v) {
+        buf.push_back((uint8_t)v);
+        buf.push_back((uint8_t)(v >> 8));
+    };
+    auto put64 = [&](uint64_t v) {
+        for (int b = 0; b < 8; ++b) buf.push_back((uint8_t)(v >> (8 * b)));
+    };
+    // put*(const char*, std::uint16_t): the length mod 65536 and that many leading bytes; the
+    // flyweight's limit is 1040 absolute (wrapForEncode(buf, 8, 1048 - 8))
+    auto put_var = [&](std::string_view v) {
+        const size_t len = v.size() & 0xffffu;
+        if (buf.size() + 2 + len > SBE_CE_FALLBACK_REC_MAX) throw std::runtime_error("buffer too short [E100]");
+        put16((uint32_t)len);
+        buf.insert(buf.end(), v.begin(), v.begin() + len);
+    };
+    put16(SBE_TM_BLOCK_LEN);
+    put16(SBE_TM_TEMPLATE_ID);
+    put16(SBE_TOPIC_SCHEMA_ID);
+    put16(1);
+    put64(now());  // timestamp
+    put64(0);      // sequenceNumber
+    put_var("_subscriptions");
+    put_var("COMMIT_OFFSET");
+    put_var(std::string("commit_offset_") + client_id + "_" + std::to_string(now()));
+    put_var(text);
+    put_var("{}");
+    return buf;
 }
 
 void CommitManager::commit_message(const std::string& topic, const std::string& message_identifier,
@@ -1806,6 +1920,7 @@ struct AutoCommitter::EmitRequest {
     std::vector<std::uint8_t> status;    // [n] SBE_CE_*
     std::vector<std::uint64_t> out_off;  // [n + 1]
     std::vector<std::uint8_t> frames;    // out_off[n] bytes
+    std::uint64_t now_ns = 0, uuid_ns = 0;  // json_fallback: the call's two clock readings
 };
 
 CommitPlan AutoCommitter::classify(const ParsedBatch& batch) const { return run(batch, nullptr); }
@@ -1832,6 +1947,9 @@ CommitPlan AutoCommitter::run(const ParsedBatch& batch, EmitRequest* emit) const
     if (n == 0) return plan;
     const Descriptors& d = *batch.desc_;
     const uint64_t lo = batch.rec_off_[0], bytes = batch.rec_off_[n] - lo;
+    const bool fallback = emit && emit->options->json_fallback;
+    if (fallback && client_id_.size() > SBE_COMMIT_TABLE_BYTES)
+        throw std::length_error("AutoCommitter: the default identifier holds 4096 bytes");
     // staged inputs: offsets (rebased), status, flags, view offsets and lengths, the table, the records
     const size_t o_st = al16((n + 1) * 8), o_fl = o_st + al16(n), o_vo = o_fl + al16(n), o_vl = o_vo + al16(20 * n),
                  o_ta = o_vl + al16(20 * n), o_to = o_ta + SBE_COMMIT_TABLE_BYTES,
@@ -1840,7 +1958,9 @@ CommitPlan AutoCommitter::run(const ParsedBatch& batch, EmitRequest* emit) const
                  o_ia = o_tid + (emit ? al16(4 * SBE_COMMIT_MAX_TOPICS) : 0),
                  o_io = o_ia + (emit ? SBE_COMMIT_TABLE_BYTES : 0),
                  o_seq = o_io + (emit ? al16(4 * (SBE_COMMIT_MAX_TOPICS + 1)) : 0), o_mask = o_seq + (emit ? al16(8 * n) : 0),
-                 o_data = o_mask + (emit ? al16(n) : 0), stage = o_data + (size_t)bytes + 16;
+                 // json_fallback only: the records' timestamps, the default identifier (client_id)
+                 o_ts = o_mask + (emit ? al16(n) : 0), o_di = o_ts + (fallback ? al16(8 * n) : 0),
+                 o_data = o_di + (fallback ? SBE_COMMIT_TABLE_BYTES : 0), stage = o_data + (size_t)bytes + 16;
     Ctx& c = ctx();
     Pipeline::Slot& s = c.pipe.slot[0];  // serial use of the pipeline's first slot (idle between calls)
     hipStream_t stream = c.batch_stream();
@@ -1887,8 +2007,13 @@ CommitPlan AutoCommitter::run(const ParsedBatch& batch, EmitRequest* emit) const
             for (size_t i = x; i < y; ++i) {
                 sq[i] = d.seq(i);
                 if (masked) hp[o_mask + i] = (*emit->callback_ok)[i] ? 1 : 0;
+                if (fallback) reinterpret_cast<uint64_t*>(hp + o_ts)[i] = (uint64_t)batch.timestamp(i);
             }
         });
+        if (fallback) {
+            std::memcpy(hp + o_di, client_id_.data(), client_id_.size());
+            ident_max = std::max(ident_max, client_id_.size());
+        }
     }
     if (bytes)
         for_ranges((size_t)bytes, size_t(1) << 18, [&](size_t x, size_t y) {
@@ -1901,7 +2026,9 @@ CommitPlan AutoCommitter::run(const ParsedBatch& batch, EmitRequest* emit) const
     // emit only: status, offsets, totals, the workspace and the frames
     const int framed = emit && emit->options->session_frame ? 1 : 0;
     const size_t wsb = emit ? sbe_commit_emit_workspace_size(n) : 0,
-                 bound = emit ? (size_t)sbe_commit_emit_output_bound(n, bytes + n * ident_max, framed) : 0,
+                 bound = !emit      ? 0
+                         : fallback ? (size_t)sbe_commit_fallback_output_bound(n, bytes + n * ident_max, framed)
+                                    : (size_t)sbe_commit_emit_output_bound(n, bytes + n * ident_max, framed),
                  p_est = outb, p_eoff = p_est + al16(n), p_tot = p_eoff + al16(8 * (n + 1)), p_ws = p_tot + 32,
                  p_frames = p_ws + al16(wsb);
     s.d_out.need(emit ? p_frames + bound : outb);
@@ -1924,16 +2051,20 @@ CommitPlan AutoCommitter::run(const ParsedBatch& batch, EmitRequest* emit) const
         fail("sbe_classify_commits");
     }
     if (emit) {  // the plan is read where classify wrote it
-        const sbe_decoded dec_seq{dec.status, dec.flags, nullptr, nullptr, dec.view_off, dec.view_len,
-                                  reinterpret_cast<uint64_t*>(di + o_seq)};
+        const sbe_decoded dec_seq{dec.status,   dec.flags,    nullptr, fallback ? reinterpret_cast<uint64_t*>(di + o_ts) : nullptr,
+                                  dec.view_off, dec.view_len, reinterpret_cast<uint64_t*>(di + o_seq)};
+        const sbe_commit_fallback fb{di + o_ta,      reinterpret_cast<const uint32_t*>(di + o_to),
+                                     di + o_di,      (uint32_t)client_id_.size(),
+                                     emit->now_ns,   emit->uuid_ns};
         const sbe_commit_emit_out res{reinterpret_cast<uint64_t*>(dq + p_eoff), dq + p_est, nullptr,
                                       reinterpret_cast<uint64_t*>(dq + p_tot)};
-        if (sbe_emit_commit_offsets(di + o_data, reinterpret_cast<const uint64_t*>(di), n, &dec_seq, &out,
-                                    reinterpret_cast<const uint32_t*>(di + o_tid), di + o_ia,
-                                    reinterpret_cast<const uint32_t*>(di + o_io), k, masked ? di + o_mask : nullptr,
-                                    emit->options->last_only ? SBE_CE_LAST_ONLY : 0u, framed,
-                                    emit->options->leadership_term_id, emit->options->cluster_session_id,
-                                    dq + p_frames, bound, &res, dq + p_ws, wsb, stream) != SBE_OK) {
+        if (sbe_emit_commit_offsets_ex(di + o_data, reinterpret_cast<const uint64_t*>(di), n, &dec_seq, &out,
+                                       reinterpret_cast<const uint32_t*>(di + o_tid), di + o_ia,
+                                       reinterpret_cast<const uint32_t*>(di + o_io), k, masked ? di + o_mask : nullptr,
+                                       emit->options->last_only ? SBE_CE_LAST_ONLY : 0u, framed,
+                                       emit->options->leadership_term_id, emit->options->cluster_session_id,
+                                       dq + p_frames, bound, &res, dq + p_ws, wsb, stream,
+                                       fallback ? &fb : nullptr) != SBE_OK) {
             c.abort_all();
             fail("sbe_emit_commit_offsets");
         }
@@ -2024,7 +2155,11 @@ CommitSendResult AutoCommitter::commit_and_send_batch(const ParsedBatch& batch, 
         throw std::invalid_argument("AutoCommitter: one callback result per record");
     if (callback_ok && options.last_only)
         throw std::invalid_argument("AutoCommitter: last_only sends what an unmasked commit_batch commits");
-    EmitRequest emit{&options, callback_ok, {}, {}, {}};
+    EmitRequest emit{&options, callback_ok, {}, {}, {}, 0, 0};
+    if (options.json_fallback) {  // the call's two clock readings: timestamp, then uuid
+        emit.now_ns = options.clock ? options.clock() : now_nanos_sys();
+        emit.uuid_ns = options.clock ? options.clock() : now_nanos_sys();
+    }
     const CommitPlan plan = run(batch, &emit);
     CommitSendResult r;
     r.commits = commit_batch(batch, plan, commits, callback_ok);
@@ -2033,21 +2168,49 @@ CommitSendResult AutoCommitter::commit_and_send_batch(const ParsedBatch& batch, 
         ++r.offered;
         if (offer(p, len)) ++r.accepted;
     };
+    auto session_header = [&] {  // `frame` = the SessionMessageHeader (src/session_manager.cpp:936-967), or empty
+        frame.clear();
+        if (!options.session_frame) return;
+        const std::uint16_t h[4] = {SBE_SESSION_BLOCK_LEN, SBE_SESSION_TEMPLATE_ID, SBE_CLUSTER_SCHEMA_ID,
+                                    SBE_CLUSTER_SCHEMA_VERSION};
+        const std::int64_t ids[3] = {options.leadership_term_id, options.cluster_session_id, 0};
+        frame.resize(SBE_SESSION_HDR_LEN);
+        std::memcpy(frame.data(), h, 8);  // little-endian host, as the rest of the mirror
+        std::memcpy(frame.data() + 8, ids, 24);
+    };
     for (std::size_t i = 0; i < batch.size(); ++i) {
         const std::uint8_t st = emit.status[i];
-        if (st == SBE_CE_EMITTED) {
+        if (st == SBE_CE_EMITTED || st == SBE_CE_EMITTED_JSON) {
             send(emit.frames.data() + emit.out_off[i], (std::size_t)(emit.out_off[i + 1] - emit.out_off[i]));
         } else if (st == SBE_CE_E109_MESSAGE_ID) {
             r.too_long.push_back(i);
+        } else if (st == SBE_CE_E100_FALLBACK) {
+            r.fallback_e100.push_back(i);
         } else if (st == SBE_CE_HOST) {
             const bool entry = plan.topic_idx[i] < plan.table.size();  // a table entry whose topic has id 0
             if (options.last_only && entry && plan.last[plan.topic_idx[i]] != i) continue;
             const std::string t = entry ? plan.table[plan.topic_idx[i]] : topic(batch, plan, i);
+            const std::string_view id = batch.view(i, 2);
             if (CommitManager::topic_to_id(t) == 0) {
-                r.unsent.push_back(i);
+                if (!options.json_fallback) {
+                    r.unsent.push_back(i);
+                    continue;
+                }
+                // the device's convention: the call's first reading, then the second + i
+                const CommitOffset off{t, message_identifier(t), std::string(id), (std::uint64_t)batch.timestamp(i),
+                                       batch.sequence_number(i)};
+                int reads = 0;
+                try {
+                    const std::vector<std::uint8_t> rec = commits.build_commit_offset_fallback(
+                        off.message_identifier, off, [&] { return reads++ ? emit.uuid_ns + i : emit.now_ns; });
+                    session_header();
+                    frame.insert(frame.end(), rec.begin(), rec.end());
+                    send(frame.data(), frame.size());
+                } catch (const std::runtime_error&) {  // "buffer too short [E100]"
+                    r.fallback_e100.push_back(i);
+                }
                 continue;
             }
-            const std::string_view id = batch.view(i, 2);
             if (id.size() > SBE_VAR_MAX_LEN) {
                 r.too_long.push_back(i);
                 continue;
@@ -2055,15 +2218,7 @@ CommitSendResult AutoCommitter::commit_and_send_batch(const ParsedBatch& batch, 
             const CommitOffset off{t, message_identifier(t), std::string(id), (std::uint64_t)batch.timestamp(i),
                                    batch.sequence_number(i)};
             const std::vector<std::uint8_t> rec = commits.build_commit_offset_message(t, client_id_, off);
-            frame.clear();
-            if (options.session_frame) {  // SessionMessageHeader (src/session_manager.cpp:936-967)
-                const std::uint16_t h[4] = {SBE_SESSION_BLOCK_LEN, SBE_SESSION_TEMPLATE_ID, SBE_CLUSTER_SCHEMA_ID,
-                                            SBE_CLUSTER_SCHEMA_VERSION};
-                const std::int64_t ids[3] = {options.leadership_term_id, options.cluster_session_id, 0};
-                frame.resize(SBE_SESSION_HDR_LEN);
-                std::memcpy(frame.data(), h, 8);  // little-endian host, as the rest of the mirror
-                std::memcpy(frame.data() + 8, ids, 24);
-            }
+            session_header();
             frame.insert(frame.end(), rec.begin(), rec.end());
             send(frame.data(), frame.size());
         }

@@ -516,10 +516,27 @@ public:
     // src/commit_manager.cpp:16-22
     static std::uint32_t topic_to_id(const std::string& topic);
     // src/commit_manager.cpp:107-132: a known topic → CommitOffsetLite (template 301) with topicId,
-    // sequence, messageId, messageIdentifier; E109 → std::runtime_error.  The unknown-topic
-    // fallback (a jsoncpp-formatted TopicMessage, :134-160) is not built: it throws.
+    // sequence, messageId, messageIdentifier; E109 → std::runtime_error.  For an unknown topic
+    // (topic_to_id 0) this call still throws, as it always has: build_commit_offset_fallback builds
+    // the reference's frame for it.
     std::vector<std::uint8_t> build_commit_offset_message(const std::string& topic, const std::string& client_id,
                                                           const CommitOffset& offset) const;
+    // src/commit_manager.cpp:197-209: the jsoncpp text of an offset, indentation "" (keys sorted, no
+    // white space): {"action":"COMMIT_OFFSET","messageIdentifier":..,"message_id":..,
+    // "sequence_number":..,"timestamp_nanos":..,"topic":..}.  Host-only code, as Order::validate.
+    // (parse_commit_offset needs a tree-building reader and stays out.)
+    static std::string serialize_commit_offset(const CommitOffset& offset);
+    // src/commit_manager.cpp:134-175, the unknown-topic branch of build_commit_offset_message on
+    // the host, without a GPU: the TopicMessage {16,1,1,1} on "_subscriptions" of type
+    // "COMMIT_OFFSET" with uuid "commit_offset_" + client_id + "_" + clock() and the text above as
+    // payload, headers "{}".  Both of the reference's length quirks are kept: uuid and payload hold
+    // their length mod 65536 and that many leading bytes (the std::uint16_t overloads), and a
+    // record of more than 1040 bytes throws std::runtime_error("buffer too short [E100]") (the
+    // 1048-byte buffer wrapped at 8).  The clock (default: the system's nanoseconds) is read twice,
+    // first for the timestamp, then for the uuid, as the reference reads it.
+    using ClockFn = std::function<std::uint64_t()>;
+    std::vector<std::uint8_t> build_commit_offset_fallback(const std::string& client_id, const CommitOffset& offset,
+                                                           const ClockFn& clock = {}) const;
     // Batch (one GPU launch); every offset's topic must be known.
     EncodedBatch build_commit_offset_batch(const std::vector<CommitOffset>& offsets) const;
     // src/commit_manager.cpp:29-35: the last commit per "topic:message_identifier"
@@ -549,6 +566,13 @@ struct CommitSendOptions {
     std::int64_t cluster_session_id = 0;
     bool session_frame = true;  // false: the bare CommitOffsetLite records
     bool last_only = false;     // one frame per topic-table entry (SBE_CE_LAST_ONLY)
+    // Send the reference's JSON TopicMessage (src/commit_manager.cpp:134-175) for topics without a
+    // numeric id instead of reporting them `unsent`.  The call reads `clock` (default: the system's
+    // nanoseconds) twice: every JSON frame carries the first reading as its timestamp, and record
+    // i's uuid ends in the second reading + i (sbe_emit_commit_offsets_ex's convention; the
+    // reference reads the clock per record).
+    bool json_fallback = false;
+    std::function<std::uint64_t()> clock;
 };
 struct CommitSendResult {
     std::size_t commits = 0;            // commit_message calls made (commit_batch's return value)
@@ -556,6 +580,8 @@ struct CommitSendResult {
     std::size_t accepted = 0;           // of those, the ones the sink returned true for
     std::vector<std::size_t> unsent;    // committed records whose topic has id 0, ascending
     std::vector<std::size_t> too_long;  // committed records whose message_id exceeds 65534 bytes
+    std::vector<std::size_t> fallback_e100;  // json_fallback: records whose JSON record exceeds 1040 bytes
+                                             // (the reference throws "buffer too short [E100]")
 };
 
 // The commit branch of ClusterClient::handle_incoming_message (src/cluster_client.cpp:1251-1288)
@@ -599,9 +625,16 @@ public:
     // them); the plan and the emit result come back in one download, the frames, whose size the
     // emit result gives, in the copy after it.  A record whose topic the device table does not
     // resolve (SBE_CE_HOST) is resolved here: with a non-zero topic_to_id its frame is built by
-    // build_commit_offset_message and offered at its place; with topic id 0 (the reference's JSON
-    // fallback, not built) its index goes to `unsent`, and nothing throws.  A message_id over
-    // 65534 bytes (the reference throws E109) goes to `too_long`.
+    // build_commit_offset_message and offered at its place; with topic id 0 its index goes to
+    // `unsent`, and nothing throws.  A message_id over 65534 bytes (the reference throws E109) goes
+    // to `too_long`.
+    // options.json_fallback: the emit call is sbe_emit_commit_offsets_ex with a fallback, so the
+    // device also builds the JSON frame of every id-0 table entry and of every plain string topic
+    // outside the table (identifier: client_id), offered at their place in record order; the
+    // records still left to the host (escaped or non-string topics) with id 0 get the same frame
+    // from build_commit_offset_fallback.  `unsent` is then always empty; records whose frame the
+    // reference could not build go to `fallback_e100`.  std::length_error when client_id exceeds
+    // 4096 bytes.
     // last_only: only the last committable record of every table entry is sent (what commit_batch
     // commits without a mask); std::invalid_argument together with callback_ok.
     // std::length_error when the identifiers of the table exceed 4096 bytes.

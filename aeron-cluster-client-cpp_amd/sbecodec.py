@@ -118,6 +118,11 @@ class _CommitEmitOut(ctypes.Structure):
                 ("totals", ctypes.c_void_p)]
 
 
+class _CommitFallback(ctypes.Structure):
+    _fields_ = [("topic_arena", ctypes.c_void_p), ("topic_off", ctypes.c_void_p), ("default_ident", ctypes.c_void_p),
+                ("default_ident_len", ctypes.c_uint32), ("now_ns", ctypes.c_uint64), ("uuid_ns", ctypes.c_uint64)]
+
+
 class _AckOut(ctypes.Structure):
     _fields_ = [("code", ctypes.c_void_p), ("base_ns", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
 
@@ -198,6 +203,12 @@ def _load():
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
             ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.POINTER(_CommitEmitOut), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    if hasattr(lib, "sbe_emit_commit_offsets_ex"):
+        lib.sbe_commit_fallback_output_bound.restype = ctypes.c_uint64
+        lib.sbe_commit_fallback_output_bound.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
+        lib.sbe_emit_commit_offsets_ex.restype = ctypes.c_int
+        lib.sbe_emit_commit_offsets_ex.argtypes = lib.sbe_emit_commit_offsets.argtypes + [
+            ctypes.POINTER(_CommitFallback)]
     lib.sbe_inflight_table_size.restype = ctypes.c_size_t
     lib.sbe_inflight_table_size.argtypes = [ctypes.c_uint64]
     lib.sbe_inflight_workspace_size.restype = ctypes.c_size_t
@@ -647,7 +658,19 @@ def classify_commits(data, rec_off, dec: Decoded, topics, out: CommitPlan | None
 
 # sbe_emit_commit_offsets: per-record status and the flag (include/sbecodec.h)
 CE_NONE, CE_EMITTED, CE_HOST, CE_E109_MESSAGE_ID, CE_OVERFLOW = range(5)
+CE_EMITTED_JSON, CE_E100_FALLBACK = 5, 6  # with a CommitFallback only
 CE_LAST_ONLY = 0x1
+CE_FALLBACK_REC_MAX = 1040
+
+
+@dataclass
+class CommitFallback:
+    """The legacy COMMIT_OFFSET TopicMessage (src/commit_manager.cpp:134-175) for the records
+    emit_commit_offsets would leave as CE_HOST because their topic has no numeric id."""
+    topic_table: object         # the classify call's topics: a list of bytes or its (arena, off) device pair
+    default_identifier: object  # bytes or a uint8 device tensor: the identifier of topics outside the table
+    now_ns: int                 # TopicMessage.timestamp of every JSON frame of the call
+    uuid_ns: int                # record i's uuid ends in the decimal of uuid_ns + i
 
 
 @dataclass
@@ -682,10 +705,14 @@ def commit_emit_output_bound(n: int, id_bytes: int, session: bool = True) -> int
     return int(lib().sbe_commit_emit_output_bound(n, id_bytes, 1 if session else 0))
 
 
+def commit_fallback_output_bound(n: int, id_bytes: int, session: bool = True) -> int:
+    return int(lib().sbe_commit_fallback_output_bound(n, id_bytes, 1 if session else 0))
+
+
 def emit_commit_offsets(data, rec_off, dec: Decoded, plan: CommitPlan, topic_ids, identifiers, mask=None, flags=0,
                         session=True, leadership_term_id=0, cluster_session_id=0, out=None, out_capacity=None,
                         out_off=None, status=None, emit_idx=None, totals=None, workspace=None,
-                        stream=None) -> CommitFrames:
+                        stream=None, fallback: CommitFallback | None = None) -> CommitFrames:
     """The CommitOffsetLite frame of every record classify_commits committed, compacted in record
     order on the device (send_commit_offset, src/cluster_client.cpp:1264-1278): `plan` is
     classify_commits' result for the same data / rec_off / dec and a table of k entries.
@@ -695,7 +722,10 @@ def emit_commit_offsets(data, rec_off, dec: Decoded, plan: CommitPlan, topic_ids
     out: a uint8 device tensor (no alignment needed); out_capacity = 0 without `out` only sizes
     (out_off / totals hold the full layout).  With neither, `out` is allocated at the bound
     n * (24 [+ 32]) + the records' bytes + n * the longest identifier, which reads the identifier
-    offsets back once when `identifiers` is a device pair."""
+    offsets back once when `identifiers` is a device pair.
+    fallback: a CommitFallback; the call then goes through sbe_emit_commit_offsets_ex, which also
+    emits the JSON TopicMessage of topics without an id (CE_EMITTED_JSON, CE_E100_FALLBACK) and
+    resolves plain string topics outside the table."""
     data = _dev(data, torch.uint8, "data")
     rec_off = _dev(rec_off, torch.int64, "rec_off")
     n = int(rec_off.numel()) - 1
@@ -718,13 +748,32 @@ def emit_commit_offsets(data, rec_off, dec: Decoded, plan: CommitPlan, topic_ids
     mask = _dev(mask, torch.uint8, "mask")
     if mask is not None and mask.numel() < n:
         raise SbeError("mask is shorter than the batch")
+    if fallback is not None:
+        if not hasattr(lib(), "sbe_emit_commit_offsets_ex"):
+            raise SbeError("this libsbecodec.so has no sbe_emit_commit_offsets_ex")
+        t = fallback.topic_table
+        fb_arena, fb_off = t if isinstance(t, tuple) else commit_topic_table(t, dev)
+        fb_arena = _dev(fb_arena, torch.uint8, "fallback topic arena")
+        fb_off = _dev(fb_off, torch.int32, "fallback topic offsets")
+        if fb_arena.numel() < COMMIT_TABLE_BYTES or fb_off.numel() != k + 1:
+            raise SbeError("the fallback's topic table must be the classify call's table")
+        fb_ident = fallback.default_identifier
+        if not isinstance(fb_ident, torch.Tensor):
+            import numpy as np
+            fb_ident = torch.from_numpy(np.frombuffer(bytes(fb_ident), np.uint8).copy()).to(dev)
+        fb_ident = _dev(fb_ident, torch.uint8, "default identifier")
+        # an empty identifier still needs a pointer
+        fb_ident_ptr = fb_ident if fb_ident.numel() else torch.zeros(16, dtype=torch.uint8, device=dev)
     if out is None and out_capacity is None:
         if isinstance(identifiers, tuple):
             o = off.cpu()
             longest = int((o[1:] - o[:-1]).clamp(min=0).max().item()) if k else 0
         else:
             longest = max((len(bytes(t)) for t in identifiers), default=0)
-        out_capacity = commit_emit_output_bound(n, int(data.numel()) + n * min(longest, COMMIT_TABLE_BYTES), session)
+        if fallback is not None:
+            longest = max(longest, int(fb_ident.numel()))
+        bound = commit_emit_output_bound if fallback is None else commit_fallback_output_bound
+        out_capacity = bound(n, int(data.numel()) + n * min(longest, COMMIT_TABLE_BYTES), session)
     if out is None and out_capacity:
         out = torch.empty(int(out_capacity), dtype=torch.uint8, device=dev)
     out = _dev(out, torch.uint8, "out")
@@ -745,12 +794,15 @@ def emit_commit_offsets(data, rec_off, dec: Decoded, plan: CommitPlan, topic_ids
                  None if dec.seq is None else _dev(dec.seq, torch.int64, "dec.seq").data_ptr())
     p = _CommitOut(*(getattr(plan, f).data_ptr() for f, _ in _COMMIT_KEYS))
     r = _CommitEmitOut(out_off.data_ptr(), status.data_ptr(), emit_idx.data_ptr(), totals.data_ptr())
-    rc = lib().sbe_emit_commit_offsets(_ptr(data), _ptr(rec_off), n, ctypes.byref(d), ctypes.byref(p),
-                                       _ptr(topic_ids), _ptr(arena), _ptr(off), k, _ptr(mask), int(flags),
-                                       1 if session else 0, int(leadership_term_id), int(cluster_session_id),
-                                       _ptr(out), cap, ctypes.byref(r), _ptr(workspace), workspace.numel(),
-                                       _stream(stream))
-    _check(rc, "sbe_emit_commit_offsets")
+    args = (_ptr(data), _ptr(rec_off), n, ctypes.byref(d), ctypes.byref(p), _ptr(topic_ids), _ptr(arena), _ptr(off),
+            k, _ptr(mask), int(flags), 1 if session else 0, int(leadership_term_id), int(cluster_session_id),
+            _ptr(out), cap, ctypes.byref(r), _ptr(workspace), workspace.numel(), _stream(stream))
+    if fallback is None:
+        _check(lib().sbe_emit_commit_offsets(*args), "sbe_emit_commit_offsets")
+    else:
+        fb = _CommitFallback(fb_arena.data_ptr(), fb_off.data_ptr(), fb_ident_ptr.data_ptr(), int(fb_ident.numel()),
+                             int(fallback.now_ns) & (2**64 - 1), int(fallback.uuid_ns) & (2**64 - 1))
+        _check(lib().sbe_emit_commit_offsets_ex(*args, ctypes.byref(fb)), "sbe_emit_commit_offsets_ex")
     return CommitFrames(out, out_off[: n + 1], status[:n], emit_idx[:n], totals[:3], workspace)
 
 

@@ -427,7 +427,8 @@ int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n,
 #define SBE_CE_EMITTED 1u         /* the frame is out[out_off[i] .. out_off[i+1]) */
 #define SBE_CE_HOST 2u            /* topic_idx[i] >= k (SBE_TOPIC_UNKNOWN, SBE_TOPIC_HOST) or topic_id of the
                                      entry is 0: the host resolves the topic, or owes the reference's JSON
-                                     fallback (src/commit_manager.cpp:134-175, not built); 0 bytes */
+                                     fallback (src/commit_manager.cpp:134-175), which
+                                     sbe_emit_commit_offsets_ex builds on the device; 0 bytes */
 #define SBE_CE_E109_MESSAGE_ID 3u /* messageId over 65534 bytes: computeLength throws [E109]; 0 bytes */
 #define SBE_CE_OVERFLOW 4u        /* the frame ends past out_capacity: not written, and no byte of out from the
                                      end of the last frame that fits is touched */
@@ -471,6 +472,73 @@ int sbe_emit_commit_offsets(const uint8_t* in, const uint64_t* rec_off, uint64_t
                             int session, int64_t leadership_term_id, int64_t cluster_session_id, uint8_t* out,
                             uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* ---- the legacy COMMIT_OFFSET TopicMessage for topics without a numeric id ----
+ * CommitManager::topic_to_id (src/commit_manager.cpp:16-22) knows four names; for every other
+ * topic build_commit_offset_message takes its fallback (:134-175): a TopicMessage
+ *   [the 32-B SessionMessageHeader when `session`]
+ *   header {16,1,1,1}, u64 timestamp = now_ns, u64 sequenceNumber = 0, u16 + "_subscriptions",
+ *   u16 + "COMMIT_OFFSET", u16 + uuid, u16 + text, u16 + "{}"
+ * with uuid = "commit_offset_" + messageIdentifier + "_" + decimal clock (send_commit_offset passes
+ * offset.message_identifier as client_id, src/cluster_client.cpp:678) and text = the jsoncpp object
+ * written with indentation "" (keys sorted, no white space; also serialize_commit_offset :197-209):
+ *   {"action":"COMMIT_OFFSET","messageIdentifier":Q,"message_id":Q,"sequence_number":D,
+ *    "timestamp_nanos":D,"topic":Q}
+ * Q = valueToQuotedStringN(.., emitUTF8 = false), D = unsigned decimal; message_id and
+ * sequence_number as in the Lite frame, timestamp_nanos = dec->ts[i].
+ * Two quirks of the reference are kept.  putUuid / putPayload take the length as std::uint16_t
+ * (TopicMessage.h:865-879): a field of L bytes stores L mod 65536 and that many leading bytes.
+ * The flyweight is wrapped with wrapForEncode(buf, 8, 1048 - 8) and its positions are absolute
+ * (TopicMessage.h:210-219, 267-274), so with u and p the two stored lengths the record is
+ * 63 + u + p bytes and the reference throws "buffer too short [E100]" exactly when that exceeds
+ * 1040 (this path has no computeLength, hence no E109).
+ *
+ * With fb != NULL the status of record i is the first line that applies:
+ *   1. SBE_CE_NONE as above.
+ *   2. A table entry with topic_id != 0: the Lite frame as above (EMITTED, E109, OVERFLOW).
+ *   3. A table entry with topic_id == 0: the JSON frame, topic = the entry's text in fb's topic
+ *      table, messageIdentifier = the entry's identifier; under SBE_CE_LAST_ONLY only the entry's
+ *      last record (the others SBE_CE_NONE).
+ *   4. topic_idx == SBE_TOPIC_UNKNOWN and topic_kind == SBE_TOPIC_KIND_STRING: topic = the token
+ *      plan->topic_off / topic_len (kept inside the record), messageIdentifier = default_ident; the
+ *      Lite frame with id 1..4 when the token is one of topic_to_id's names, else the JSON frame.
+ *      SBE_CE_LAST_ONLY does not filter these records.
+ *   5. SBE_CE_HOST: SBE_TOPIC_HOST, and SBE_TOPIC_UNKNOWN with an escaped string. */
+#define SBE_CE_EMITTED_JSON 5u  /* the JSON frame is out[out_off[i] .. out_off[i+1]) */
+#define SBE_CE_E100_FALLBACK 6u /* 63 + u + p > 1040: the reference throws [E100]; 0 bytes */
+#define SBE_CE_FALLBACK_REC_MAX 1040u
+
+typedef struct sbe_commit_fallback {
+    const uint8_t* topic_arena;   /* the classify call's topic table (device), clamped the same way */
+    const uint32_t* topic_off;    /* [k + 1] */
+    const uint8_t* default_ident; /* device; config_.client_id; readable for default_ident_len bytes */
+    uint32_t default_ident_len;   /* <= SBE_COMMIT_TABLE_BYTES */
+    uint64_t now_ns;              /* TopicMessage.timestamp of every JSON frame of the call */
+    uint64_t uuid_ns;             /* record i's uuid ends in the decimal of uuid_ns + i */
+} sbe_commit_fallback;
+
+/* Upper bound of the frames of n records under a fallback: each at most the larger of its Lite
+ * frame and SBE_CE_FALLBACK_REC_MAX + SBE_SESSION_HDR_LEN (id_bytes as for
+ * sbe_commit_emit_output_bound). */
+uint64_t sbe_commit_fallback_output_bound(uint64_t n, uint64_t id_bytes, int session);
+
+/* sbe_emit_commit_offsets with the fallback fb; fb == NULL is sbe_emit_commit_offsets itself (the
+ * same launches, the same results).  The reference reads the clock per record (twice: timestamp
+ * and uuid); a batch has one reading, so every JSON frame carries now_ns and record i's uuid ends
+ * in uuid_ns + i, which keeps the uuids of one call distinct and ascending.  That convention has
+ * no reference counterpart.  out_off, emit_idx and totals keep their meaning: totals[0] counts
+ * frames of either kind (EMITTED, EMITTED_JSON, OVERFLOW), totals[2] the SBE_CE_HOST records left.
+ * Workspace: sbe_commit_emit_workspace_size(n), lengths and block sums, never text.
+ * With fb, dec->ts, plan->topic_kind, plan->topic_off and plan->topic_len are read as well.
+ * SBE_EINVAL as for sbe_emit_commit_offsets, and (whatever n is) a null member pointer of fb,
+ * default_ident_len > SBE_COMMIT_TABLE_BYTES, a misaligned fb->topic_off; for n > 0 a null or
+ * misaligned dec->ts / plan->topic_kind / topic_off / topic_len. */
+int sbe_emit_commit_offsets_ex(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                               const sbe_commit_out* plan, const uint32_t* topic_id, const uint8_t* ident_arena,
+                               const uint32_t* ident_off, uint32_t k, const uint8_t* mask, uint32_t flags,
+                               int session, int64_t leadership_term_id, int64_t cluster_session_id, uint8_t* out,
+                               uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
+                               size_t workspace_bytes, void* stream, const sbe_commit_fallback* fb);
 
 /* ================================= ack correlation ================================= */
 /* The step of the client's message loop that joins the two directions: publish_topic remembers

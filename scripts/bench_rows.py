@@ -17,6 +17,8 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
   commit_emit            1 M decoded and classified fixed-256 Orders, all committed → session-framed
                          CommitOffsetLite frames in one fused call (sbe_emit_commit_offsets), and in the
                          same run sbe_encode_lite_batch on a pre-gathered arena of the same ids
+  commit_fallback        the commit_emit batch with a table whose entries all have id 0 → session-framed
+                         JSON COMMIT_OFFSET TopicMessages (sbe_emit_commit_offsets_ex with a fallback)
   ack_correlate          1 M "pub_<nanos>" uuids remembered in a 2 M-slot in-flight table, then 1 M full
                          acks (about 10 % unknown ids, 1 % repeated ids) decoded on-egress and matched;
                          remember, match and the decode of the same ack batch timed in the same run, and
@@ -586,6 +588,60 @@ def row_commit_emit(steps, warmup):
           "baseline: sbe_encode_lite_batch on a pre-gathered arena (no gather, no session frame)": (ms_b, nb_b)})
 
 
+def row_commit_fallback(steps, warmup):
+    """sbe_emit_commit_offsets_ex with a fallback over the commit_emit batch (1 M decoded and
+    classified fixed-256 Orders, every header's topic a table entry) and a table in which every
+    entry has id 0: every record emits the session-framed JSON TopicMessage.  Bytes per record, as
+    the commit_emit row counts them: rec_off 8, cm 1, topic_idx 4, status + flags 2, view 2 offset
+    and length 8, seq 8, ts 8 and the id read; out_off 8, status 1, emit_idx 8 and the frame
+    written."""
+    n = 1_000_000
+    arena, L, ts = T.fixed256_orders(n)
+    a2 = arena.reshape(n, 222).copy()
+    a2[:, 190:] = np.frombuffer(b'{"topic":"orders","a":"CREATE"} ', np.uint8)
+    data, off = T.oracle_encode(a2.reshape(-1), L, ts)[:2]
+    topics = [b"orders", b"order_request_topic", b"order_notification_topic"]
+    idents = [b"client-01", b"sub-req", b"sub-ntf"]
+    d0, o0 = dev(data, torch.uint8), dev(np.asarray(off, np.uint64), torch.int64)
+    table = sbecodec.commit_topic_table(topics, "cuda")
+    itab = sbecodec.commit_identifier_table(idents, "cuda")
+    tid = dev(np.zeros(3, np.uint32), torch.int32)
+    fb = sbecodec.CommitFallback(table, b"client-01", 1_700_000_000_123_456_789, 1_700_000_000_223_456_789)
+    w = int(np.asarray(L).reshape(n, 5)[0, 2])
+
+    def make(k):
+        d, o = d0.clone(), o0.clone()
+        dec = sbecodec.decode_batch(d, o, sbecodec.DEC_PARSE_MESSAGE, out=sbecodec.alloc_decoded(n, "cuda"),
+                                    in_bytes=data.size, seq=True)
+        plan = sbecodec.classify_commits(d, o, dec, table)
+        sized = sbecodec.emit_commit_offsets(d, o, dec, plan, tid, itab, leadership_term_id=7, cluster_session_id=9,
+                                             out=None, out_capacity=0, fallback=fb)
+        torch.cuda.synchronize()
+        fr = sbecodec.emit_commit_offsets(d, o, dec, plan, tid, itab, leadership_term_id=7, cluster_session_id=9,
+                                          out_capacity=int(sized.totals[1]), out_off=sized.out_off, status=sized.status,
+                                          emit_idx=sized.emit_idx, totals=sized.totals, workspace=sized.workspace,
+                                          fallback=fb)
+        return d, o, dec, plan, fr
+
+    R = Rot(make)
+    torch.cuda.synchronize()
+    fr0 = R.sets[0][4]
+    assert int(fr0.totals[0]) == n and int(fr0.status.min()) == int(fr0.status.max()) == sbecodec.CE_EMITTED_JSON
+    total = int(fr0.totals[1])
+
+    def fn():
+        d, o, dec, plan, fr = R.next()
+        sbecodec.emit_commit_offsets(d, o, dec, plan, tid, itab, leadership_term_id=7, cluster_session_id=9,
+                                     out=fr.out, out_off=fr.out_off, status=fr.status, emit_idx=fr.emit_idx,
+                                     totals=fr.totals, workspace=fr.workspace, fallback=fb)
+
+    ms = _event_ms(fn, steps, warmup)
+    nb = n * (8 + 1 + 4 + 2 + 8 + 8 + 8 + w) + n * (8 + 1 + 8) + total
+    print(json.dumps({"row": "commit_fallback", "id_bytes": w, "frame_bytes": total // n}), flush=True)
+    line("commit_fallback", n, ms * 1e-3,
+         {"sbe_emit_commit_offsets_ex (fallback, every record a session-framed JSON frame: all launches)": (ms, nb)})
+
+
 def row_ack_correlate(steps, warmup):
     """sbe_inflight_remember of 1 M publish_topic uuids into an empty 2 M-slot table, then
     sbe_inflight_match_acks of 1 M full acks (T.ack_wire; about 10 % ids nobody sent, 1 % ids that
@@ -679,7 +735,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,commit_emit,ack_correlate")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,commit_emit,commit_fallback,ack_correlate")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -710,6 +766,8 @@ def main():
             row_autocommit(args.steps, args.warmup)
         elif r == "commit_emit":
             row_commit_emit(args.steps, args.warmup)
+        elif r == "commit_fallback":
+            row_commit_fallback(args.steps, args.warmup)
         elif r == "ack_correlate":
             row_ack_correlate(args.steps, args.warmup)
         elif r.startswith("lite"):
