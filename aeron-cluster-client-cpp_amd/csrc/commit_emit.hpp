@@ -12,6 +12,10 @@
 // both block-sum arrays, the writing launch (one wave per 64-record tile through an LDS window, as
 // publish_write).  No atomics: two calls give identical results.  The workspace holds the frame
 // lengths and the block sums, never text.
+//
+// commit_fallback.hpp builds on this file: the record-level helpers below (ce_entry, ce_view,
+// ce_seq, ce_session_header) and the two launch-level ones in namespace ce (size_tail, write_head)
+// are the one copy both kernel pairs run.
 #pragma once
 
 // ---- one record (also compiled for the host: tests/commitsend/emit_host_check.cpp) ----
@@ -36,22 +40,34 @@ struct CeIn {
     int64_t term, sess;
 };
 
-// identifier of table entry j: offsets clamped to the table size, a reversed entry is empty
-__device__ __forceinline__ uint32_t ce_ident(const CeIn& a, uint32_t j, const uint8_t*& p) {
-    const uint32_t o0 = a.ioff[j] < SBE_COMMIT_TABLE_BYTES ? a.ioff[j] : SBE_COMMIT_TABLE_BYTES;
-    const uint32_t o1 = a.ioff[j + 1] < SBE_COMMIT_TABLE_BYTES ? a.ioff[j + 1] : SBE_COMMIT_TABLE_BYTES;
-    p = a.iarena + o0;
+// Entry j of an offset table over `arena` (the identifier table here, the topic table of the
+// fallback): offsets clamped to the table size, a reversed entry is empty.
+__device__ __forceinline__ uint32_t ce_entry(const uint8_t* arena, const uint32_t* off, uint32_t j, const uint8_t*& p) {
+    const uint32_t o0 = off[j] < SBE_COMMIT_TABLE_BYTES ? off[j] : SBE_COMMIT_TABLE_BYTES;
+    const uint32_t o1 = off[j + 1] < SBE_COMMIT_TABLE_BYTES ? off[j + 1] : SBE_COMMIT_TABLE_BYTES;
+    p = arena + o0;
     return o1 > o0 ? o1 - o0 : 0u;
 }
-// message_id of record i: view 2, kept inside the record whatever the descriptors say
-__device__ __forceinline__ uint32_t ce_msg_id(const CeIn& a, uint64_t i, const uint8_t*& p) {
+// Bytes [vo, vo + vl) of record i, kept inside the record whatever the descriptors say.
+__device__ __forceinline__ uint32_t ce_view(const CeIn& a, uint64_t i, uint32_t vo, uint32_t vl, const uint8_t*& p) {
     const uint64_t b = a.rec_off[i], e = a.rec_off[i + 1];
     const uint64_t L64 = e > b ? e - b : 0;
     const uint32_t L = L64 > 0xffffffffull ? 0xffffffffu : (uint32_t)L64;
-    const uint32_t vo = a.view_off[5 * i + 2], vl = a.view_len[5 * i + 2];
     const uint32_t o = vo <= L ? vo : L;
     p = a.in + b + o;
     return vl <= L - o ? vl : L - o;
+}
+__device__ __forceinline__ uint32_t ce_ident(const CeIn& a, uint32_t j, const uint8_t*& p) {
+    return ce_entry(a.iarena, a.ioff, j, p);
+}
+// message_id of record i: view 2
+__device__ __forceinline__ uint32_t ce_msg_id(const CeIn& a, uint64_t i, const uint8_t*& p) {
+    return ce_view(a, i, a.view_off[5 * i + 2], a.view_len[5 * i + 2], p);
+}
+// decode writes seq only for flagged TopicMessages: every other record's sequence_number is 0
+__device__ __forceinline__ uint64_t ce_seq(const CeIn& a, uint64_t i) {
+    const bool has_seq = a.seq && a.st[i] == SBE_ST_TM && (a.fl[i] & (SBE_FL_SEQ_KEY | SBE_FL_SEQ_ESC));
+    return has_seq ? a.seq[i] : 0ull;
 }
 __device__ __forceinline__ uint32_t ce_frame_len(const CeIn& a, uint32_t idn, uint32_t identn) {
     return (a.session ? SBE_SESSION_HDR_LEN : 0u) + SBE_LITE_OVERHEAD(2u) + idn + identn;
@@ -89,25 +105,27 @@ __device__ __forceinline__ CeFields ce_fields(const CeIn& a, uint64_t i) {
     CeFields f;
     const uint32_t j = a.tidx[i];
     f.tid = a.topic_id[j];
-    // decode writes seq only for flagged TopicMessages: every other record's sequence_number is 0
-    const bool has_seq = a.seq && a.st[i] == SBE_ST_TM && (a.fl[i] & (SBE_FL_SEQ_KEY | SBE_FL_SEQ_ESC));
-    f.seq = has_seq ? a.seq[i] : 0ull;
+    f.seq = ce_seq(a, i);
     f.idn = ce_msg_id(a, i, f.id);
     f.identn = ce_ident(a, j, f.ident);
     return f;
 }
+// The SessionMessageHeader (src/session_manager.cpp:936-967) in front of a frame, where the call asks for it.
+template <class S>
+__device__ __forceinline__ void ce_session_header(S& s, const CeIn& a) {
+    if (!a.session) return;
+    ce_put16(s, SBE_SESSION_BLOCK_LEN);
+    ce_put16(s, SBE_SESSION_TEMPLATE_ID);
+    ce_put16(s, SBE_CLUSTER_SCHEMA_ID);
+    ce_put16(s, SBE_CLUSTER_SCHEMA_VERSION);
+    ce_put64(s, (uint64_t)a.term);
+    ce_put64(s, (uint64_t)a.sess);
+    ce_put64(s, 0);
+}
 // The frame through sink s (put(byte)); copy(s, p, n) appends n bytes at p.
 template <class S, class Copy>
 __device__ __forceinline__ void ce_frame(S& s, const CeIn& a, const CeFields& f, Copy copy) {
-    if (a.session) {  // SessionMessageHeader (src/session_manager.cpp:936-967)
-        ce_put16(s, SBE_SESSION_BLOCK_LEN);
-        ce_put16(s, SBE_SESSION_TEMPLATE_ID);
-        ce_put16(s, SBE_CLUSTER_SCHEMA_ID);
-        ce_put16(s, SBE_CLUSTER_SCHEMA_VERSION);
-        ce_put64(s, (uint64_t)a.term);
-        ce_put64(s, (uint64_t)a.sess);
-        ce_put64(s, 0);
-    }
+    ce_session_header(s, a);
     ce_put16(s, SBE_LITE_BLOCK_LEN);
     ce_put16(s, SBE_COMMIT_OFFSET_LITE_TEMPLATE_ID);
     ce_put16(s, SBE_TOPIC_SCHEMA_ID);
@@ -126,8 +144,8 @@ namespace ce {
 
 using namespace oj;
 
-struct CeArgs {
-    CeIn c;
+// What a call writes and the workspace it works in: shared by both kernel pairs (commit_fallback.hpp).
+struct CeOut {
     uint64_t n;
     uint8_t* out;
     uint64_t cap;
@@ -143,19 +161,16 @@ struct CeArgs {
     uint64_t* blk_bytes;
     uint64_t* blk_cnt;
 };
+struct CeArgs {
+    CeIn c;
+    CeOut o;
+};
 
-// Sizing launch: status and frame bytes per record, the block's sums.  Entry nblk of both sum
-// arrays is zeroed here, so that the exclusive scan leaves the batch totals there.
-__global__ __launch_bounds__(kBlock) void commit_emit_measure(CeArgs a) {
-    __shared__ uint64_t wtot[kBlock / kWave];
-    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+// The tail of a sizing launch, once the record's verdict st and frame bytes len are known: the
+// block's sums.  Entry nblk of both sum arrays is zeroed here, so that the exclusive scan leaves
+// the batch totals there.
+__device__ __forceinline__ void size_tail(const CeOut& a, uint32_t st, uint32_t len, uint64_t* wtot) {
     const uint32_t lane = threadIdx.x % kWave, wv = threadIdx.x / kWave;
-    uint32_t len = 0, st = SBE_CE_NONE;
-    if (i < a.n) {
-        st = ce_size_one(a.c, i, len);
-        a.status[i] = (uint8_t)st;
-        a.sz[i] = len;
-    }
     uint64_t bytes, cnt;
     (void)block_excl_scan(len, wtot, lane, wv, bytes);
     (void)block_excl_scan((len ? 1ull : 0ull) | (st == SBE_CE_HOST ? 1ull << 32 : 0ull), wtot, lane, wv, cnt);
@@ -166,27 +181,16 @@ __global__ __launch_bounds__(kBlock) void commit_emit_measure(CeArgs a) {
     }
 }
 
-// Writing launch: one wave per tile of 64 records.  A typical framed record is ~100 bytes (32 + 24
-// + a 36-byte id + a short identifier), so a tile's frames fit the window in one pass; a frame
-// larger than the window goes from its lane straight to HBM (write_staged).  Every frame is at
-// least 24 bytes, which write_staged's window passes rely on.
-#ifndef SBE_CE_WIN
-#define SBE_CE_WIN 8192
-#endif
-constexpr uint32_t kCeWin = SBE_CE_WIN;
-static_assert(kCeWin >= 4096 && kCeWin % 16 == 0 && kBlock % kWWave == 0, "a writing tile lies inside one sizing block");
-
-__global__ __launch_bounds__(kWWave) void commit_emit_write(CeArgs a) {
-    __shared__ __attribute__((aligned(16))) uint8_t win[kCeWin];
-    const uint32_t lane = threadIdx.x;
-    const uint64_t i0 = (uint64_t)blockIdx.x * kWWave, i = i0 + lane;
-    const bool live = i < a.n;
-    // this record's length and, for an emitter, everything its frame holds: loaded first, so that
-    // the loads are in flight while the offsets are worked out
-    const uint64_t len = live ? a.sz[i] : 0;
-    CeFields f{};
-    if (len) f = ce_fields(a.c, i);
-    // offsets and ranks: the block's prefixes, the block's records before the tile, the tile's scan
+// The head of a writing launch, for the lane whose record i = i0 + lane has a frame of len bytes
+// (0: none): the frame's place [o, e) from the block's prefix, the block's records before the tile
+// and the tile's scan; out_off, emit_idx and the totals stored; todo: the frame fits the capacity
+// (SBE_CE_OVERFLOW stored where it does not).
+struct Place {
+    uint64_t o, e;
+    bool todo;
+};
+__device__ __forceinline__ Place write_head(const CeOut& a, uint64_t i0, uint32_t lane, uint64_t len) {
+    const uint64_t i = i0 + lane;
     const uint64_t bs = i0 / kBlock * kBlock;
     uint64_t pre = 0, prc = 0;
 #pragma unroll
@@ -201,7 +205,7 @@ __global__ __launch_bounds__(kWWave) void commit_emit_write(CeArgs a) {
     prc = ((a.blk_cnt[i0 / kBlock] - bytes_total) & 0xffffffffull) + wave_sum64(prc);
     const uint64_t o = pre + wave_incl_scan64(len, (int)lane) - len, e = o + len;
     const uint64_t emitters = __ballot(len != 0);
-    if (live) {
+    if (i < a.n) {
         a.out_off[i] = o;
         if (i + 1 == a.n) a.out_off[a.n] = e;
         if (len && a.emit_idx) a.emit_idx[prc + __popcll(emitters & ((1ull << lane) - 1))] = i;
@@ -214,7 +218,42 @@ __global__ __launch_bounds__(kWWave) void commit_emit_write(CeArgs a) {
     }
     const bool todo = len && e <= a.cap;
     if (len && !todo) a.status[i] = SBE_CE_OVERFLOW;
-    write_staged<kCeWin>(a.out, (lw8*)win, lane, todo, o, e, [&](auto& s) {
+    return Place{o, e, todo};
+}
+
+// Sizing launch: status and frame bytes per record (size_tail).
+__global__ __launch_bounds__(kBlock) void commit_emit_measure(CeArgs a) {
+    __shared__ uint64_t wtot[kBlock / kWave];
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    uint32_t len = 0, st = SBE_CE_NONE;
+    if (i < a.o.n) {
+        st = ce_size_one(a.c, i, len);
+        a.o.status[i] = (uint8_t)st;
+        a.o.sz[i] = len;
+    }
+    size_tail(a.o, st, len, wtot);
+}
+// Writing launch: one wave per tile of 64 records.  A typical framed record is ~100 bytes (32 + 24
+// + a 36-byte id + a short identifier), so a tile's frames fit the window in one pass; a frame
+// larger than the window goes from its lane straight to HBM (write_staged).  Every frame is at
+// least 24 bytes, which write_staged's window passes rely on.
+#ifndef SBE_CE_WIN
+#define SBE_CE_WIN 8192
+#endif
+constexpr uint32_t kCeWin = SBE_CE_WIN;
+static_assert(kCeWin >= 4096 && kCeWin % 16 == 0 && kBlock % kWWave == 0, "a writing tile lies inside one sizing block");
+
+__global__ __launch_bounds__(kWWave) void commit_emit_write(CeArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t win[kCeWin];
+    const uint32_t lane = threadIdx.x;
+    const uint64_t i0 = (uint64_t)blockIdx.x * kWWave, i = i0 + lane;
+    // this record's length and, for an emitter, everything its frame holds: loaded first, so that
+    // the loads are in flight while the offsets are worked out
+    const uint64_t len = i < a.o.n ? a.o.sz[i] : 0;
+    CeFields f{};
+    if (len) f = ce_fields(a.c, i);
+    const auto [o, e, todo] = write_head(a.o, i0, lane, len);
+    write_staged<kCeWin>(a.o.out, (lw8*)win, lane, todo, o, e, [&](auto& s) {
         ce_frame(s, a.c, f, [](auto& t, const uint8_t* p, uint32_t m) { t = pub::raw(t, (gu8*)p, m); });
     });
 }

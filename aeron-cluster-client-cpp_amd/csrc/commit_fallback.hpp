@@ -18,7 +18,10 @@
 //
 // Launches as commit_emit.hpp: sizing (the text is measured with a counting sink), the scan over
 // the block sums, writing (the record composed straight into the LDS window; the payload clipped
-// by a sink that stops).  The workspace holds lengths and block sums, never text.
+// by a sink that stops).  The workspace holds lengths and block sums, never text.  The block sums
+// of the sizing launch and the offsets, ranks and totals of the writing launch are commit_emit.hpp's
+// (ce::size_tail, ce::write_head), as are the clamped table entry, the view kept inside its
+// record, the sequence rule and the session header (ce_entry, ce_view, ce_seq, ce_session_header).
 #pragma once
 
 // ---- one record (also compiled for the host: tests/commitfallback/fallback_host_check.cpp) ----
@@ -74,23 +77,6 @@ __device__ __forceinline__ uint32_t cf_name_id(const uint8_t* p, uint32_t n) {
         if (p[k] != (uint8_t)nm[k]) return 0;
     return id;
 }
-// the topic token of record i, kept inside the record as ce_msg_id keeps the id
-__device__ __forceinline__ uint32_t cf_token(const CfIn& a, uint64_t i, const uint8_t*& p) {
-    const uint64_t b = a.c.rec_off[i], e = a.c.rec_off[i + 1];
-    const uint64_t L64 = e > b ? e - b : 0;
-    const uint32_t L = L64 > 0xffffffffull ? 0xffffffffu : (uint32_t)L64;
-    const uint32_t vo = a.tok_off[i], vl = a.tok_len[i];
-    const uint32_t o = vo <= L ? vo : L;
-    p = a.c.in + b + o;
-    return vl <= L - o ? vl : L - o;
-}
-// topic of table entry j, clamped as the classifier clamps it
-__device__ __forceinline__ uint32_t cf_entry(const CfIn& a, uint32_t j, const uint8_t*& p) {
-    const uint32_t o0 = a.toff[j] < SBE_COMMIT_TABLE_BYTES ? a.toff[j] : SBE_COMMIT_TABLE_BYTES;
-    const uint32_t o1 = a.toff[j + 1] < SBE_COMMIT_TABLE_BYTES ? a.toff[j + 1] : SBE_COMMIT_TABLE_BYTES;
-    p = a.tarena + o0;
-    return o1 > o0 ? o1 - o0 : 0u;
-}
 
 // What a record that sbe_emit_commit_offsets reports as SBE_CE_HOST becomes under a fallback.
 enum : uint32_t { kCfHost = 0, kCfSkip = 1, kCfLite = 2, kCfJson = 3 };
@@ -110,10 +96,10 @@ __device__ __forceinline__ CfRec cf_record(const CfIn& a, uint64_t i) {
             return r;
         }
         r.what = kCfJson;
-        r.topicn = cf_entry(a, j, r.topic);
+        r.topicn = ce_entry(a.tarena, a.toff, j, r.topic);  // clamped as the classifier clamps it
         r.identn = ce_ident(a.c, j, r.ident);
     } else if (j == SBE_TOPIC_UNKNOWN && a.kind[i] == SBE_TOPIC_KIND_STRING) {
-        r.topicn = cf_token(a, i, r.topic);
+        r.topicn = ce_view(a.c, i, a.tok_off[i], a.tok_len[i], r.topic);  // the topic token
         r.ident = a.dident;
         r.identn = a.didentn;
         r.tid = cf_name_id(r.topic, r.topicn);
@@ -122,13 +108,15 @@ __device__ __forceinline__ CfRec cf_record(const CfIn& a, uint64_t i) {
         r.what = kCfHost;
         return r;
     }
-    const bool has_seq =
-        a.c.seq && a.c.st[i] == SBE_ST_TM && (a.c.fl[i] & (SBE_FL_SEQ_KEY | SBE_FL_SEQ_ESC));
-    r.seq = has_seq ? a.c.seq[i] : 0ull;
+    r.seq = ce_seq(a.c, i);
     r.ts = a.ts[i];
     r.uuid = a.uuid_ns + i;
     r.idn = ce_msg_id(a.c, i, r.id);
     return r;
+}
+// The fields of a kCfLite record's frame: a CommitOffsetLite through ce_frame.
+__device__ __forceinline__ CeFields cf_lite_fields(const CfRec& r) {
+    return CeFields{r.tid, r.idn, r.identn, r.seq, r.id, r.ident};
 }
 
 // The text (commit_manager.cpp:135-145, = serialize_commit_offset :197-209) through sink s.
@@ -187,15 +175,7 @@ __device__ __forceinline__ void cf_frame(S& s, const CfIn& a, const CfRec& r, ui
                                          Dec dec) {
     const uint32_t u = cf_uuid_len(r);
     const uint32_t p = len - (a.c.session ? SBE_SESSION_HDR_LEN : 0u) - kCfRecFixed - u;
-    if (a.c.session) {  // SessionMessageHeader (src/session_manager.cpp:936-967)
-        ce_put16(s, SBE_SESSION_BLOCK_LEN);
-        ce_put16(s, SBE_SESSION_TEMPLATE_ID);
-        ce_put16(s, SBE_CLUSTER_SCHEMA_ID);
-        ce_put16(s, SBE_CLUSTER_SCHEMA_VERSION);
-        ce_put64(s, (uint64_t)a.c.term);
-        ce_put64(s, (uint64_t)a.c.sess);
-        ce_put64(s, 0);
-    }
+    ce_session_header(s, a.c);
     ce_put16(s, SBE_TM_BLOCK_LEN);
     ce_put16(s, SBE_TM_TEMPLATE_ID);
     ce_put16(s, SBE_TOPIC_SCHEMA_ID);
@@ -255,7 +235,7 @@ struct ClipOut {
 
 struct CfArgs {
     CfIn f;
-    ce::CeArgs e;  // e.c is not read: f.c holds the same
+    ce::CeOut o;
 };
 
 __device__ __forceinline__ uint64_t text_bytes(const CfRec& r) {
@@ -269,21 +249,13 @@ __device__ __forceinline__ uint64_t text_bytes(const CfRec& r) {
 __global__ __launch_bounds__(kBlock) void commit_fallback_measure(CfArgs a) {
     __shared__ uint64_t wtot[kBlock / kWave];
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    const uint32_t lane = threadIdx.x % kWave, wv = threadIdx.x / kWave;
     uint32_t len = 0, st = SBE_CE_NONE;
-    if (i < a.e.n) {
+    if (i < a.o.n) {
         st = cf_size_one(a.f, i, len, [](const CfRec& r) { return text_bytes(r); });
-        a.e.status[i] = (uint8_t)st;
-        a.e.sz[i] = len;
+        a.o.status[i] = (uint8_t)st;
+        a.o.sz[i] = len;
     }
-    uint64_t bytes, cnt;
-    (void)block_excl_scan(len, wtot, lane, wv, bytes);
-    (void)block_excl_scan((len ? 1ull : 0ull) | (st == SBE_CE_HOST ? 1ull << 32 : 0ull), wtot, lane, wv, cnt);
-    if (threadIdx.x == 0) {
-        a.e.blk_bytes[blockIdx.x] = bytes;
-        a.e.blk_cnt[blockIdx.x] = cnt;
-        if (blockIdx.x == 0) a.e.blk_bytes[gridDim.x] = a.e.blk_cnt[gridDim.x] = 0;
-    }
+    ce::size_tail(a.o, st, len, wtot);
 }
 
 // Writing launch: one wave per tile of 64 records, as commit_emit_write.  A JSON frame with short
@@ -305,8 +277,7 @@ __global__ __launch_bounds__(kWWave, SBE_CF_MINW) void commit_fallback_write(CfA
     __shared__ __attribute__((aligned(16))) uint8_t win[kCfWin];
     const uint32_t lane = threadIdx.x;
     const uint64_t i0 = (uint64_t)blockIdx.x * kWWave, i = i0 + lane;
-    const bool live = i < a.e.n;
-    const uint64_t len = live ? a.e.sz[i] : 0;
+    const uint64_t len = i < a.o.n ? a.o.sz[i] : 0;
     // an emitter's fields: a table entry with an id as commit_emit_write has them, the others from
     // cf_record (a Lite frame of a named token through the same CeFields)
     bool json = false;
@@ -319,42 +290,11 @@ __global__ __launch_bounds__(kWWave, SBE_CF_MINW) void commit_fallback_write(CfA
         } else {
             r = cf_record(a.f, i);
             json = r.what == kCfJson;
-            f.tid = r.tid;
-            f.idn = r.idn;
-            f.identn = r.identn;
-            f.seq = r.seq;
-            f.id = r.id;
-            f.ident = r.ident;
+            f = cf_lite_fields(r);
         }
     }
-    const uint64_t bs = i0 / kBlock * kBlock;
-    uint64_t pre = 0, prc = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kBlock / kWave; ++q) {
-        const uint64_t k = bs + lane + kWave * q;
-        const uint32_t s = k < i0 ? a.e.sz[k] : 0u;
-        pre += s;
-        prc += s ? 1u : 0u;
-    }
-    pre = a.e.blk_bytes[i0 / kBlock] + wave_sum64(pre);
-    const uint64_t bytes_total = a.e.blk_cnt[0];  // what the scan carried into the counts
-    prc = ((a.e.blk_cnt[i0 / kBlock] - bytes_total) & 0xffffffffull) + wave_sum64(prc);
-    const uint64_t o = pre + wave_incl_scan64(len, (int)lane) - len, e = o + len;
-    const uint64_t emitters = __ballot(len != 0);
-    if (live) {
-        a.e.out_off[i] = o;
-        if (i + 1 == a.e.n) a.e.out_off[a.e.n] = e;
-        if (len && a.e.emit_idx) a.e.emit_idx[prc + __popcll(emitters & ((1ull << lane) - 1))] = i;
-    }
-    if (blockIdx.x == 0 && lane == 0) {
-        const uint64_t nblk = (a.e.n + kBlock - 1) / kBlock, c = a.e.blk_cnt[nblk] - bytes_total;
-        a.e.totals[0] = c & 0xffffffffull;
-        a.e.totals[1] = bytes_total;
-        a.e.totals[2] = c >> 32;
-    }
-    const bool todo = len && e <= a.e.cap;
-    if (len && !todo) a.e.status[i] = SBE_CE_OVERFLOW;
-    write_staged<kCfWin>(a.e.out, (lw8*)win, lane, todo, o, e, [&](auto& s0) {
+    const auto [o, e, todo] = ce::write_head(a.o, i0, lane, len);
+    write_staged<kCfWin>(a.o.out, (lw8*)win, lane, todo, o, e, [&](auto& s0) {
         typedef ClipOut<std::remove_reference_t<decltype(s0)>> Out;
         Out s(s0, len);
         auto copy = [](Out& t, const uint8_t* p, uint32_t m) { t = pub::raw(t, (gu8*)p, (uint64_t)m); };

@@ -4987,6 +4987,34 @@ int serve_encode_host(sbe_server* s, const EncReq& q, uint64_t n, uint64_t ts_de
     return serve_call(s, r);
 }
 
+// What the batch entry points below check and carve with.  A null pointer is aligned.
+bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+uintptr_t align16(uintptr_t x) { return (x + 15) & ~(uintptr_t)15; }
+// A workspace handed out piece by piece, every piece on a 16-byte boundary.  The caller has
+// checked the size against the entry point's *_workspace_size, whose terms mirror the takes.
+struct Carver {
+    uintptr_t at;
+    explicit Carver(void* workspace) : at(reinterpret_cast<uintptr_t>(workspace)) {}
+    template <class T>
+    T* take(uint64_t count) {
+        at = align16(at);
+        T* p = reinterpret_cast<T*>(at);
+        at += count * sizeof(T);
+        return p;
+    }
+};
+
+// The launches of sbe_emit_commit_offsets_ex for either kernel pair: sizing, one scan over both
+// block-sum arrays as one, writing.
+template <class Args>
+int commit_launches(void (*measure)(Args), void (*write)(Args), const Args& a, const ce::CeOut& o, hipStream_t s) {
+    const uint64_t nblk = (o.n + oj::kBlock - 1) / oj::kBlock;
+    hipLaunchKernelGGL(measure, dim3((uint32_t)nblk), dim3(oj::kBlock), 0, s, a);
+    hipLaunchKernelGGL(oj::order_json_scan_blocks, dim3(1), dim3(oj::kScanThreads), 0, s, o.blk_bytes, 2 * (nblk + 1));
+    hipLaunchKernelGGL(write, dim3((uint32_t)((o.n + oj::kWWave - 1) / oj::kWWave)), dim3(oj::kWWave), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
 }  // namespace
 
 // ============================================================================================
@@ -5410,7 +5438,7 @@ int sbe_materialize_views(const uint8_t* in, const uint64_t* rec_off, uint64_t n
     const uint64_t nb = (n + kMatBlk - 1) / kMatBlk;      // mat_sums blocks
     const uint64_t nt = (n + kMatTile - 1) / kMatTile;    // copy waves
     if (nt > 0xffffffffull) return SBE_EINVAL;
-    uint64_t* bsum = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
+    uint64_t* bsum = Carver(workspace).take<uint64_t>(nb + nt);  // the block sums, the tile sums behind them
     MatArgs a{in, rec_off, n, dec->status, dec->view_off, dec->view_len, arena, arena_capacity, arena_off, bsum, bsum + nb};
     hipLaunchKernelGGL(mat_sums, dim3((uint32_t)nb), dim3(kMatBlk), 0, s, a);
     hipLaunchKernelGGL(mat_scan_blocks, dim3(1), dim3(kMatBlk), 0, s, a, nb);
@@ -5425,16 +5453,16 @@ int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n,
                          const uint8_t* topic_arena, const uint32_t* topic_off, uint32_t k,
                          const sbe_commit_out* out, void*, size_t, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
-    if (!out || !out->last || !out->count || mis(out->last, 7) || mis(out->count, 7)) return SBE_EINVAL;
+    if (!out || !out->last || !out->count || misaligned(out->last, 7) || misaligned(out->count, 7)) return SBE_EINVAL;
     if (k == 0 || k > SBE_COMMIT_MAX_TOPICS) return SBE_EINVAL;
     // an empty batch only initialises last / count: its per-record arrays may be null
     if (n && (!in || !rec_off || !dec || !dec->status || !dec->flags || !dec->view_off || !dec->view_len ||
               !topic_arena || !topic_off || !out->cm || !out->topic_src || !out->topic_kind || !out->topic_off ||
               !out->topic_len || !out->topic_idx))
         return SBE_EINVAL;
-    if (n && (mis(rec_off, 7) || mis(dec->view_off, 3) || mis(dec->view_len, 3) || mis(topic_off, 3) ||
-              mis(out->topic_off, 3) || mis(out->topic_len, 3) || mis(out->topic_idx, 3)))
+    if (n && (misaligned(rec_off, 7) || misaligned(dec->view_off, 3) || misaligned(dec->view_len, 3) ||
+              misaligned(topic_off, 3) || misaligned(out->topic_off, 3) || misaligned(out->topic_len, 3) ||
+              misaligned(out->topic_idx, 3)))
         return SBE_EINVAL;
     const uint64_t tiles = (n + kTile - 1) / kTile;
     if (tiles > 0x7fffffffull) return SBE_EINVAL;
@@ -5481,12 +5509,11 @@ int sbe_emit_commit_offsets_ex(const uint8_t* in, const uint64_t* rec_off, uint6
                                uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
                                size_t workspace_bytes, void* stream, const sbe_commit_fallback* fb) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
-    if (fb && (!fb->topic_arena || !fb->topic_off || !fb->default_ident || mis(fb->topic_off, 3) ||
+    if (fb && (!fb->topic_arena || !fb->topic_off || !fb->default_ident || misaligned(fb->topic_off, 3) ||
                fb->default_ident_len > SBE_COMMIT_TABLE_BYTES))
         return SBE_EINVAL;
-    if (!res || !res->out_off || !res->totals || mis(res->out_off, 7) || mis(res->totals, 7) ||
-        mis(res->emit_idx, 7))
+    if (!res || !res->out_off || !res->totals || misaligned(res->out_off, 7) || misaligned(res->totals, 7) ||
+        misaligned(res->emit_idx, 7))
         return SBE_EINVAL;
     if (k == 0 || k > SBE_COMMIT_MAX_TOPICS || (flags & ~SBE_CE_LAST_ONLY) || ((flags & SBE_CE_LAST_ONLY) && mask) ||
         (session != 0 && session != 1) || (!out && out_capacity) || n >= (1ull << 32))
@@ -5499,49 +5526,29 @@ int sbe_emit_commit_offsets_ex(const uint8_t* in, const uint64_t* rec_off, uint6
         !plan->cm || !plan->topic_idx || ((flags & SBE_CE_LAST_ONLY) && !plan->last) || !topic_id || !ident_arena ||
         !ident_off || !res->status || !workspace)
         return SBE_EINVAL;
-    if (mis(rec_off, 7) || mis(dec->view_off, 3) || mis(dec->view_len, 3) || mis(dec->seq, 7) ||
-        mis(plan->topic_idx, 3) || ((flags & SBE_CE_LAST_ONLY) && mis(plan->last, 7)) || mis(topic_id, 3) ||
-        mis(ident_off, 3) || mis(workspace, 15))
+    if (misaligned(rec_off, 7) || misaligned(dec->view_off, 3) || misaligned(dec->view_len, 3) ||
+        misaligned(dec->seq, 7) || misaligned(plan->topic_idx, 3) ||
+        ((flags & SBE_CE_LAST_ONLY) && misaligned(plan->last, 7)) || misaligned(topic_id, 3) ||
+        misaligned(ident_off, 3) || misaligned(workspace, 15))
         return SBE_EINVAL;
-    if (fb && (!dec->ts || !plan->topic_kind || !plan->topic_off || !plan->topic_len || mis(dec->ts, 7) ||
-               mis(plan->topic_off, 3) || mis(plan->topic_len, 3)))
+    if (fb && (!dec->ts || !plan->topic_kind || !plan->topic_off || !plan->topic_len || misaligned(dec->ts, 7) ||
+               misaligned(plan->topic_off, 3) || misaligned(plan->topic_len, 3)))
         return SBE_EINVAL;
     if (workspace_bytes < sbe_commit_emit_workspace_size(n)) return SBE_ENOSPC;
     const uint64_t nblk = (n + oj::kBlock - 1) / oj::kBlock;
-    auto al = [](uintptr_t x) { return (x + 15) & ~(uintptr_t)15; };
-    uintptr_t w = reinterpret_cast<uintptr_t>(workspace);
-    ce::CeArgs a{};
-    a.c = CeIn{in,          rec_off,   dec->status, dec->flags, dec->view_off, dec->view_len,
-               dec->seq,    plan->cm,  plan->topic_idx, plan->last, topic_id,  ident_arena,
-               ident_off,   k,         mask,        flags,      (uint32_t)session, leadership_term_id,
-               cluster_session_id};
-    a.n = n;
-    a.out = out;
-    a.cap = out_capacity;
-    a.out_off = res->out_off;
-    a.status = res->status;
-    a.emit_idx = res->emit_idx;
-    a.totals = res->totals;
-    a.sz = reinterpret_cast<uint32_t*>(w);
-    w = al(w + 4 * n);
-    a.blk_bytes = reinterpret_cast<uint64_t*>(w);
-    a.blk_cnt = a.blk_bytes + (nblk + 1);  // contiguous: one scan runs over both
-    const dim3 wgrid((uint32_t)((n + oj::kWWave - 1) / oj::kWWave));
-    if (fb) {
-        cf::CfArgs f{};
-        f.f = CfIn{a.c,           dec->ts,       plan->topic_kind,  plan->topic_off,       plan->topic_len, fb->topic_arena,
-                   fb->topic_off, fb->default_ident, fb->default_ident_len, fb->now_ns, fb->uuid_ns};
-        f.e = a;
-        hipLaunchKernelGGL(cf::commit_fallback_measure, dim3((uint32_t)nblk), dim3(oj::kBlock), 0, s, f);
-        hipLaunchKernelGGL(oj::order_json_scan_blocks, dim3(1), dim3(oj::kScanThreads), 0, s, a.blk_bytes,
-                           2 * (nblk + 1));
-        hipLaunchKernelGGL(cf::commit_fallback_write, wgrid, dim3(oj::kWWave), 0, s, f);
-        return record_hip(hipGetLastError());
-    }
-    hipLaunchKernelGGL(ce::commit_emit_measure, dim3((uint32_t)nblk), dim3(oj::kBlock), 0, s, a);
-    hipLaunchKernelGGL(oj::order_json_scan_blocks, dim3(1), dim3(oj::kScanThreads), 0, s, a.blk_bytes, 2 * (nblk + 1));
-    hipLaunchKernelGGL(ce::commit_emit_write, wgrid, dim3(oj::kWWave), 0, s, a);
-    return record_hip(hipGetLastError());
+    const CeIn c{in,          rec_off,   dec->status, dec->flags, dec->view_off, dec->view_len,
+                 dec->seq,    plan->cm,  plan->topic_idx, plan->last, topic_id,  ident_arena,
+                 ident_off,   k,         mask,        flags,      (uint32_t)session, leadership_term_id,
+                 cluster_session_id};
+    Carver ws(workspace);
+    uint32_t* sz = ws.take<uint32_t>(n);
+    uint64_t* blk = ws.take<uint64_t>(2 * (nblk + 1));  // bytes, counts behind them: one scan runs over both
+    const ce::CeOut o{n,  out, out_capacity, res->out_off, res->status, res->emit_idx, res->totals,
+                      sz, blk, blk + (nblk + 1)};
+    if (!fb) return commit_launches(ce::commit_emit_measure, ce::commit_emit_write, ce::CeArgs{c, o}, o, s);
+    const CfIn f{c,           dec->ts,       plan->topic_kind,  plan->topic_off,       plan->topic_len, fb->topic_arena,
+                 fb->topic_off, fb->default_ident, fb->default_ident_len, fb->now_ns, fb->uuid_ns};
+    return commit_launches(cf::commit_fallback_measure, cf::commit_fallback_write, cf::CfArgs{f, o}, o, s);
 }
 
 size_t sbe_inflight_table_size(uint64_t capacity) {
@@ -5565,11 +5572,11 @@ int sbe_inflight_remember(void* table, const uint8_t* arena, const uint32_t* key
                           uint32_t stride, const uint64_t* ts, uint64_t ts_default, const uint8_t* mask, uint64_t n,
                           uint8_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
-    if (!table || mis(table, 63) || n >= (1ull << 32)) return SBE_EINVAL;
+    if (!table || misaligned(table, 63) || n >= (1ull << 32)) return SBE_EINVAL;
     if (n == 0) return SBE_OK;
     if (!arena || !key_off || !key_len || !workspace || stride == 0) return SBE_EINVAL;
-    if (mis(key_off, 3) || mis(key_len, 3) || mis(ts, 7) || mis(workspace, 3)) return SBE_EINVAL;
+    if (misaligned(key_off, 3) || misaligned(key_len, 3) || misaligned(ts, 7) || misaligned(workspace, 3))
+        return SBE_EINVAL;
     if (workspace_bytes < sbe_inflight_workspace_size(n)) return SBE_ENOSPC;
     InfRemArgs a{reinterpret_cast<uint8_t*>(table), arena, key_off, key_len, stride, ts, ts_default, mask, n, status,
                  reinterpret_cast<uint32_t*>(workspace)};
@@ -5582,14 +5589,13 @@ int sbe_inflight_remember(void* table, const uint8_t* arena, const uint32_t* key
 int sbe_inflight_match_acks(void* table, const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
                             const sbe_ack_out* out, void* workspace, size_t workspace_bytes, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
-    if (!table || mis(table, 63) || n >= (1ull << 32) || !out || mis(out->counts, 7)) return SBE_EINVAL;
+    if (!table || misaligned(table, 63) || n >= (1ull << 32) || !out || misaligned(out->counts, 7)) return SBE_EINVAL;
     // an empty batch only initialises counts: its per-record arrays may be null
     if (n && (!in || !rec_off || !dec || !dec->status || !dec->ts || !dec->view_off || !dec->view_len || !out->code ||
               !out->base_ns || !workspace))
         return SBE_EINVAL;
-    if (n && (mis(rec_off, 7) || mis(dec->ts, 7) || mis(dec->view_off, 3) || mis(dec->view_len, 3) ||
-              mis(out->base_ns, 7) || mis(workspace, 3)))
+    if (n && (misaligned(rec_off, 7) || misaligned(dec->ts, 7) || misaligned(dec->view_off, 3) ||
+              misaligned(dec->view_len, 3) || misaligned(out->base_ns, 7) || misaligned(workspace, 3)))
         return SBE_EINVAL;
     if (n && workspace_bytes < sbe_inflight_workspace_size(n)) return SBE_ENOSPC;
     if (out->counts)
@@ -5630,17 +5636,12 @@ int sbe_reassemble_fragments(const uint8_t* in, const uint64_t* frag_off, const 
     if (!in || !frag_off || !flags || !out || !workspace) return SBE_EINVAL;
     if (n >= (1ull << 31)) return SBE_EINVAL;
     if (workspace_bytes < sbe_reassemble_workspace_size(n)) return SBE_ENOSPC;
-    auto al = [](uintptr_t x) { return (x + 15) & ~(uintptr_t)15; };
-    uintptr_t w = al(reinterpret_cast<uintptr_t>(workspace));
-    FragScan* el = reinterpret_cast<FragScan*>(w);
-    w = al(w + n * sizeof(FragScan));
-    FragScan* sc = reinterpret_cast<FragScan*>(w);
-    w = al(w + n * sizeof(FragScan));
-    uint64_t* msize = reinterpret_cast<uint64_t*>(w);
-    w = al(w + 8 * (n + 1));
-    uint64_t* mfirst = reinterpret_cast<uint64_t*>(w);
-    w = al(w + 8 * (n + 1));
-    uint64_t* mlast = reinterpret_cast<uint64_t*>(w);
+    Carver ws(workspace);
+    FragScan* el = ws.take<FragScan>(n);
+    FragScan* sc = ws.take<FragScan>(n);
+    uint64_t* msize = ws.take<uint64_t>(n + 1);
+    uint64_t* mfirst = ws.take<uint64_t>(n + 1);
+    uint64_t* mlast = ws.take<uint64_t>(n + 1);
     // the big-message list lives in sc[], which the fused scan does not use (n + 2 <= 4n words)
 #ifndef SBE_FRAG_BIG  // A/B builds: 0 = no big-message list (every message copied by its own wave)
 #define SBE_FRAG_BIG 1
@@ -5690,15 +5691,11 @@ int sbe_order_to_json_batch(const sbe_order_batch* in, uint64_t n, uint32_t what
     if (workspace_bytes < sbe_order_json_workspace_size(n)) return SBE_ENOSPC;
     if (!out && out_capacity) return SBE_EINVAL;
     const uint64_t nblk = (n + oj::kBlock - 1) / oj::kBlock;
-    auto al = [](uintptr_t x) { return (x + 15) & ~(uintptr_t)15; };
-    uintptr_t w = al(reinterpret_cast<uintptr_t>(workspace));
-    uint64_t* sz = reinterpret_cast<uint64_t*>(w);
-    w = al(w + 8 * n);
-    uint64_t* base = reinterpret_cast<uint64_t*>(w);
-    w = al(w + 8 * n);
-    uint64_t* blk_str = reinterpret_cast<uint64_t*>(w);
-    w = al(w + 8 * nblk);
-    uint64_t* blk_txt = reinterpret_cast<uint64_t*>(w);
+    Carver ws(workspace);
+    uint64_t* sz = ws.take<uint64_t>(n);
+    uint64_t* base = ws.take<uint64_t>(n);
+    uint64_t* blk_str = ws.take<uint64_t>(nblk);
+    uint64_t* blk_txt = ws.take<uint64_t>(nblk);
     oj::JsonArgs a{in->arena, in->str_off, in->str_len, in->customer_id, in->timestamp, in->quantity, n, what,
                    out,       out_capacity, out_off,  status,  sz,  base,  blk_str,  blk_txt};
     // sizing (per-block sums), one small scan of the block sums per chain, writing
@@ -5746,8 +5743,7 @@ int sbe_publish_orders_batch(const sbe_order_batch* orders, const sbe_order_chec
     if (!orders || !out_off) return SBE_EINVAL;
     if (flags & ~SBE_ENC_REF_TRUNCATE8) return SBE_EINVAL;  // SBE_ENC_PUBLISH_TOPIC included
     if (session != 0 && session != 1) return SBE_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(out) & 15u) || (reinterpret_cast<uintptr_t>(out_off) & 7u) ||
-        (reinterpret_cast<uintptr_t>(error_mask) & 1u) || (reinterpret_cast<uintptr_t>(workspace) & 15u))
+    if (misaligned(out, 15) || misaligned(out_off, 7) || misaligned(error_mask, 1) || misaligned(workspace, 15))
         return SBE_EINVAL;
     if (!out && out_capacity) return SBE_EINVAL;
     if (!topic && topic_len) return SBE_EINVAL;
@@ -5763,8 +5759,7 @@ int sbe_publish_orders_batch(const sbe_order_batch* orders, const sbe_order_chec
     }
     if (n == 0) return record_hip(hipMemsetAsync(out_off, 0, 8, s));
     const uint64_t nblk = (n + oj::kBlock - 1) / oj::kBlock;
-    auto al = [](uintptr_t x) { return (x + 15) & ~(uintptr_t)15; };
-    uintptr_t w = reinterpret_cast<uintptr_t>(workspace);
+    Carver ws(workspace);
     pub::PubArgs a{};
     a.j.arena = orders->arena;
     a.j.str_off = orders->str_off;
@@ -5777,17 +5772,12 @@ int sbe_publish_orders_batch(const sbe_order_batch* orders, const sbe_order_chec
     a.j.cap = out_capacity;
     a.j.out_off = out_off;
     a.j.status = status;
-    a.j.sz = reinterpret_cast<uint64_t*>(w);
-    w = al(w + 8 * n);
-    a.j.str_base = reinterpret_cast<uint64_t*>(w);
-    w = al(w + 8 * n);
-    a.tl = reinterpret_cast<uint32_t*>(w);
-    w = al(w + 8 * n);
-    a.j.blk_str = reinterpret_cast<uint64_t*>(w);
-    w = al(w + 8 * nblk);
-    a.j.blk_txt = reinterpret_cast<uint64_t*>(w);
-    w = al(w + 8 * nblk);
-    a.blk_chk = reinterpret_cast<uint64_t*>(w);
+    a.j.sz = ws.take<uint64_t>(n);
+    a.j.str_base = ws.take<uint64_t>(n);
+    a.tl = ws.take<uint32_t>(2 * n);
+    a.j.blk_str = ws.take<uint64_t>(nblk);
+    a.j.blk_txt = ws.take<uint64_t>(nblk);
+    a.blk_chk = ws.take<uint64_t>(nblk);
     if (checks) {
         a.chk_arena = checks->arena;
         a.chk_off = checks->str_off;

@@ -136,9 +136,7 @@ extern "C" int chk_emit_fb(const uint8_t* in, const uint64_t* rec_off, uint64_t 
                 } else if (tidx[i] < k) {
                     ce_frame(s, c, ce_fields(c, i), copy);
                 } else {  // a Lite frame for a named token outside the table
-                    const CfRec r = cf_record(a, i);
-                    CeFields f{r.tid, r.idn, r.identn, r.seq, r.id, r.ident};
-                    ce_frame(s, c, f, copy);
+                    ce_frame(s, c, cf_lite_fields(cf_record(a, i)), copy);
                 }
                 if (s.n != len) return -100;  // the sizing and the writing function disagree
             } else {

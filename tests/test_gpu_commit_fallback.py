@@ -86,7 +86,8 @@ def _rec(i, kind, idn=None):
 
 
 @pytest.mark.parametrize("pattern", ["all_json", "none", "alternating", "last_tile"])
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 129])
+# 257 reaches a second 256-record sizing block, 513 a third, with tiles past the second in a block
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 129, 257, 513])
 def test_small_shapes(codec, n, pattern):
     first_of_last = (n - 1) // 64 * 64
     kind = {"all_json": lambda i: "json", "none": lambda i: "none", "alternating": lambda i: "json" if i % 2 else "lite",
