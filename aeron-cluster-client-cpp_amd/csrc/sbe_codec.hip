@@ -4828,6 +4828,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 #include "inflight.hpp"
 #include "commit_emit.hpp"
 #include "commit_fallback.hpp"
+#include "json_paths.hpp"
 
 }  // namespace
 
@@ -5473,6 +5474,43 @@ int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n,
                  out->topic_kind, out->topic_off, out->topic_len, out->topic_idx, out->last, out->count};
         hipLaunchKernelGGL(sbe_commit_kernel, dim3((uint32_t)tiles), dim3(kWave), 0, s, a);
     }
+    return record_hip(hipGetLastError());
+}
+
+size_t sbe_json_extract_workspace_size(uint64_t, uint32_t) { return 0; }
+
+int sbe_json_extract_batch(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                           uint32_t view, const uint8_t* select, const sbe_json_paths* paths, sbe_json_out* out,
+                           void*, size_t, void* stream) {
+    JxArgs a{};
+    if (!out || !jx_build_trie(paths, a.trie)) return SBE_EINVAL;
+    if (dec ? (view != 3 && view != 4) : view != 0) return SBE_EINVAL;
+    if (n == 0) return SBE_OK;
+    if (!in || !rec_off || !out->doc || !out->root_kind || !out->kind || !out->off || !out->len) return SBE_EINVAL;
+    if (dec && (!dec->status || !dec->flags || !dec->view_off || !dec->view_len)) return SBE_EINVAL;
+    if (misaligned(rec_off, 7) || misaligned(out->off, 3) || misaligned(out->len, 3) ||
+        (dec && (misaligned(dec->view_off, 3) || misaligned(dec->view_len, 3))))
+        return SBE_EINVAL;
+    const uint64_t tiles = (n + kTile - 1) / kTile;
+    if (tiles > 0x7fffffffull) return SBE_EINVAL;
+    a.in = in;
+    a.rec_off = rec_off;
+    a.n = n;
+    if (dec) {
+        a.status = dec->status;
+        a.flags = dec->flags;
+        a.view_off = dec->view_off;
+        a.view_len = dec->view_len;
+    }
+    a.select = select;
+    a.view = view;
+    a.doc = out->doc;
+    a.root_kind = out->root_kind;
+    a.kind = out->kind;
+    a.off = out->off;
+    a.len = out->len;
+    hipLaunchKernelGGL(sbe_json_extract_kernel, dim3((uint32_t)tiles), dim3(kWave), kTile * a.trie.n_paths * kJxRowBytes,
+                       reinterpret_cast<hipStream_t>(stream), a);
     return record_hip(hipGetLastError());
 }
 

@@ -3317,4 +3317,286 @@ std::size_t offer_batch(const EncodedBatch& batch, const OfferFn& offer) {
     return n;
 }
 
+// ======================================================================================
+// JSON members by path (sbe_json_extract_batch): ParsedBatch::extract, extract_json_documents,
+// extract_order_ids (examples/pubsub_reconnect_test.cpp:576-620), CommitManager::parse_commit_offset
+// (src/commit_manager.cpp:177-195)
+JsonPath::JsonPath(const std::string& dotted) {
+    size_t a = 0;
+    for (;;) {
+        const size_t b = dotted.find('.', a);
+        names.push_back(dotted.substr(a, b == std::string::npos ? b : b - a));
+        if (b == std::string::npos) break;
+        a = b + 1;
+    }
+}
+
+struct JsonExtractAccess {
+    // One launch over staged records.  d: the decode descriptors (null: bare documents, view 0);
+    // piece(i): record i's bytes; out.base_ is the caller's to fill.
+    template <class Piece>
+    static void run(size_t n, const Descriptors* d, int view, const uint8_t* select, const std::vector<JsonPath>& paths,
+                    const Piece& piece, JsonFields& out) {
+        std::vector<uint8_t> depth, names;
+        std::vector<uint32_t> name_off{0};
+        for (const JsonPath& p : paths) {
+            if (p.names.size() > 255) throw std::invalid_argument("JsonPath: too many names");
+            depth.push_back((uint8_t)p.names.size());
+            for (const std::string& nm : p.names) {
+                names.insert(names.end(), nm.begin(), nm.end());
+                name_off.push_back((uint32_t)names.size());
+            }
+        }
+        names.push_back(0);  // never empty
+        const sbe_json_paths ps{(uint32_t)paths.size(), depth.data(), names.data(), name_off.data()};
+        const size_t P = paths.size();
+        out.n_paths_ = P;
+        out.doc_.assign(n, SBE_JX_NOT_SELECTED);
+        out.root_.assign(n, SBE_JX_MISSING);
+        out.kind_.assign(n * P, SBE_JX_MISSING);
+        out.off_.assign(n * P, 0);
+        out.len_.assign(n * P, 0);
+        sbe_json_out none{};
+        if (n == 0) {  // the table and the view are still checked
+            if (sbe_json_extract_batch(nullptr, nullptr, 0, nullptr, 0, nullptr, &ps, &none, nullptr, 0, nullptr) != SBE_OK ||
+                (d ? (view != 3 && view != 4) : view != 0))
+                throw std::invalid_argument("extract: bad path table or view");
+            return;
+        }
+        std::vector<uint64_t> start(n + 1, 0);
+        for (size_t i = 0; i < n; ++i) start[i + 1] = start[i] + piece(i).size();
+        const size_t bytes = (size_t)start[n];
+        const size_t o_st = al16((n + 1) * 8), o_fl = o_st + (d ? al16(n) : 0), o_vo = o_fl + (d ? al16(n) : 0),
+                     o_vl = o_vo + (d ? al16(20 * n) : 0), o_sel = o_vl + (d ? al16(20 * n) : 0),
+                     o_data = o_sel + (select ? al16(n) : 0), stage = o_data + bytes + 16;
+        Ctx& c = ctx();
+        Pipeline::Slot& s = c.pipe.slot[0];  // serial use of the pipeline's first slot (idle between calls)
+        hipStream_t stream = c.batch_stream();
+        s.pin.need(stage);
+        uint8_t* hp = s.pin.b();
+        std::memcpy(hp, start.data(), (n + 1) * 8);
+        for_ranges(n, 4096, [&](size_t x, size_t y) {
+            for (size_t i = x; i < y; ++i) {
+                if (d) {
+                    hp[o_st + i] = d->status(i);
+                    hp[o_fl + i] = d->flags(i);
+                    std::memcpy(hp + o_vo + 20 * i, d->off(i), 20);
+                    std::memcpy(hp + o_vl + 20 * i, d->len(i), 20);
+                }
+                if (select) hp[o_sel + i] = select[i];
+                const std::string_view r = piece(i);
+                if (!r.empty()) std::memcpy(hp + o_data + start[i], r.data(), r.size());
+            }
+        });
+        s.d_in.need(stage);
+        const size_t p_root = al16(n), p_kind = p_root + al16(n), p_off = p_kind + al16(n * P), p_len = p_off + al16(4 * n * P),
+                     outb = p_len + al16(4 * n * P);
+        s.d_out.need(outb);
+        hip_check(hipMemcpyAsync(s.d_in.p, hp, stage, hipMemcpyHostToDevice, stream), "H2D");
+        uint8_t* di = s.d_in.b();
+        uint8_t* dq = s.d_out.b();
+        const sbe_decoded dec{di + o_st, di + o_fl, nullptr, nullptr, reinterpret_cast<uint32_t*>(di + o_vo),
+                              reinterpret_cast<uint32_t*>(di + o_vl), nullptr};
+        sbe_json_out res{dq, dq + p_root, dq + p_kind, reinterpret_cast<uint32_t*>(dq + p_off),
+                         reinterpret_cast<uint32_t*>(dq + p_len)};
+        const int rc = sbe_json_extract_batch(di + o_data, reinterpret_cast<const uint64_t*>(di), n, d ? &dec : nullptr,
+                                              (uint32_t)view, select ? di + o_sel : nullptr, &ps, &res, nullptr, 0, stream);
+        if (rc == SBE_EINVAL) {
+            hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+            throw std::invalid_argument("extract: bad path table or view");
+        }
+        if (rc != SBE_OK) {
+            c.abort_all();
+            fail("sbe_json_extract_batch");
+        }
+        auto back = [&](void* dst, size_t off, size_t len) {
+            hip_check(hipMemcpyAsync(dst, dq + off, len, hipMemcpyDeviceToHost, stream), "D2H");
+        };
+        back(out.doc_.data(), 0, n);
+        back(out.root_.data(), p_root, n);
+        back(out.kind_.data(), p_kind, n * P);
+        back(out.off_.data(), p_off, 4 * n * P);
+        back(out.len_.data(), p_len, 4 * n * P);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    }
+    static std::vector<const char*>& base(JsonFields& f) { return f.base_; }
+};
+
+std::string_view JsonFields::token(std::size_t i, std::size_t p) const {
+    const size_t k = i * n_paths_ + p;
+    if (kind_[k] == SBE_JX_MISSING) return {};
+    return {base_[i] + off_[k], len_[k]};
+}
+
+bool JsonFields::is_string(std::size_t i, std::size_t p) const {
+    const uint8_t k = kind(i, p);
+    return k == SBE_JX_STRING || k == SBE_JX_STRING_ESC;
+}
+
+std::string JsonFields::as_string(std::size_t i, std::size_t p) const {
+    const std::string_view tok = token(i, p);
+    switch (kind(i, p)) {
+        case SBE_JX_STRING: return std::string(tok);
+        case SBE_JX_STRING_ESC: return json_unescape(tok);
+        case SBE_JX_NUMBER: return json_number_as_string(tok);
+        case SBE_JX_TRUE: return "true";
+        case SBE_JX_FALSE: return "false";
+        case SBE_JX_OBJECT:
+        case SBE_JX_ARRAY: throw std::runtime_error("Type is not convertible to string");
+        default: return "";  // null, and the null Value::get gives for a missing member
+    }
+}
+
+std::uint64_t JsonFields::as_uint64(std::size_t i, std::size_t p) const {
+    const std::string_view t = token(i, p);
+    switch (kind(i, p)) {
+        case SBE_JX_MISSING:
+        case SBE_JX_NULL:
+        case SBE_JX_FALSE: return 0;
+        case SBE_JX_TRUE: return 1;
+        case SBE_JX_NUMBER: break;
+        default: throw std::runtime_error("Value is not convertible to UInt64.");
+    }
+    // decodeNumber: an integer token that fits is an Int / UInt, everything else a real
+    size_t q = 0;
+    const bool neg = !t.empty() && t[0] == '-';
+    if (neg) ++q;
+    const uint64_t maxv = neg ? (uint64_t)1 << 63 : ~0ull, thr = maxv / 10;
+    uint64_t v = 0;
+    bool real = false;
+    while (q < t.size() && !real) {
+        const char ch = t[q++];
+        if (ch < '0' || ch > '9') {
+            real = true;
+        } else {
+            const uint64_t dg = ch - '0';
+            if (v >= thr && (v > thr || q != t.size() || dg > maxv % 10)) real = true;
+            else v = v * 10 + dg;
+        }
+    }
+    if (!real) {
+        if (neg && v) throw std::runtime_error("LargestInt out of UInt64 range");
+        return v;
+    }
+    const double dv = std::strtod(std::string(t).c_str(), nullptr);
+    if (!(dv >= 0.0 && dv < 18446744073709551616.0)) throw std::runtime_error("double out of UInt64 range");
+    return (std::uint64_t)dv;
+}
+
+JsonFields ParsedBatch::extract(const std::vector<JsonPath>& paths, int view, const std::uint8_t* select) const {
+    JsonFields f;
+    if (view != 3 && view != 4) throw std::invalid_argument("extract: view is 3 (payload) or 4 (headers)");
+    JsonExtractAccess::run(
+        n_, desc_.get(), view, select, paths,
+        [&](size_t i) {
+            return std::string_view(reinterpret_cast<const char*>(data_ + rec_off_[i]), (size_t)(rec_off_[i + 1] - rec_off_[i]));
+        },
+        f);
+    std::vector<const char*>& base = JsonExtractAccess::base(f);
+    base.resize(n_);
+    for (size_t i = 0; i < n_; ++i) base[i] = reinterpret_cast<const char*>(data_ + rec_off_[i]);
+    return f;
+}
+
+JsonFields extract_json_documents(const std::vector<std::string>& docs, const std::vector<JsonPath>& paths) {
+    JsonFields f;
+    JsonExtractAccess::run(docs.size(), nullptr, 0, nullptr, paths, [&](size_t i) { return std::string_view(docs[i]); }, f);
+    std::vector<const char*>& base = JsonExtractAccess::base(f);
+    base.resize(docs.size());
+    for (size_t i = 0; i < docs.size(); ++i) base[i] = docs[i].data();
+    return f;
+}
+
+namespace {
+const std::vector<JsonPath>& order_id_paths() {
+    static const std::vector<JsonPath> paths{"message",
+                                             "message.message",
+                                             "message.message.client_order_id",
+                                             "message.message.order_id",
+                                             "message.message.order_details",
+                                             "message.message.order_details.client_order_id",
+                                             "message.order_details",
+                                             "message.order_details.client_order_id",
+                                             "uuid"};
+    return paths;
+}
+// the callback's body for one parsed document (:592-619)
+OrderIds order_ids_of(const JsonFields& f, size_t i) {
+    OrderIds ids;
+    if (f.doc(i) != SBE_JX_OK) return ids;        // empty payload, parse failure, or the stack limit's exception
+    if (f.root_kind(i) != SBE_JX_OBJECT) return ids;  // null: no member anywhere; anything else: isMember throws
+    auto find_str = [&](size_t p) { return f.is_string(i, p) ? f.as_string(i, p) : std::string(); };
+    const bool msg_obj = f.kind(i, 0) == SBE_JX_OBJECT;
+    if (msg_obj && f.kind(i, 1) == SBE_JX_OBJECT) {  // inner.isObject()
+        ids.client_order_id = find_str(2);
+        ids.order_id = find_str(3);
+        if (ids.client_order_id.empty() && f.kind(i, 4) == SBE_JX_OBJECT) ids.client_order_id = find_str(5);
+    } else if (msg_obj && f.kind(i, 6) == SBE_JX_OBJECT) {  // the older format
+        ids.client_order_id = find_str(7);
+    }
+    if (ids.order_id.empty()) ids.order_id = find_str(8);
+    return ids;
+}
+bool order_callback_looks(const ParseResult& r) {  // :578-579
+    return r.is_order_message() || (r.is_topic_message() && r.message_type == "CREATE_ORDER");
+}
+}  // namespace
+
+std::vector<OrderIds> extract_order_ids(const ParsedBatch& batch) {
+    const size_t n = batch.size();
+    std::vector<uint8_t> select(n, 0);
+    for_ranges(n, 1024, [&](size_t x, size_t y) {
+        ParseResult r;
+        for (size_t i = x; i < y; ++i) {
+            if (batch.status(i) != SBE_ST_TM) continue;
+            batch.result_into(i, r);
+            select[i] = order_callback_looks(r) ? 1 : 0;
+        }
+    });
+    const JsonFields f = batch.extract(order_id_paths(), 3, select.data());
+    std::vector<OrderIds> out(n);
+    for_ranges(n, 1024, [&](size_t x, size_t y) {
+        for (size_t i = x; i < y; ++i) out[i] = order_ids_of(f, i);
+    });
+    return out;
+}
+
+OrderIds extract_order_ids(const ParseResult& result) {
+    if (!order_callback_looks(result) || result.payload.empty()) return {};
+    const std::vector<std::string> docs{result.payload};
+    return order_ids_of(extract_json_documents(docs, order_id_paths()), 0);
+}
+
+std::vector<CommitOffset> CommitManager::parse_commit_offsets_batch(const std::vector<std::string>& payloads,
+                                                                    std::vector<std::string>* errors) {
+    static const std::vector<JsonPath> paths{"topic", "message_identifier", "message_id", "timestamp_nanos",
+                                             "sequence_number"};
+    const JsonFields f = extract_json_documents(payloads, paths);
+    std::vector<CommitOffset> out(payloads.size());
+    if (errors) errors->assign(payloads.size(), "");
+    for (size_t i = 0; i < payloads.size(); ++i) {
+        try {
+            if (f.doc(i) == SBE_JX_STACK) throw std::runtime_error("Exceeded stackLimit in readValue().");  // the reader's own
+            if (f.doc(i) != SBE_JX_OK) throw std::runtime_error("Failed to parse commit offset JSON: document does not parse");
+            if (f.root_kind(i) != SBE_JX_OBJECT && f.root_kind(i) != SBE_JX_NULL)  // Value::get
+                throw std::runtime_error("in Json::Value::find(begin, end): requires objectValue or nullValue");
+            CommitOffset o;
+            o.topic = f.as_string(i, 0);
+            o.message_identifier = f.as_string(i, 1);
+            o.message_id = f.as_string(i, 2);
+            o.timestamp_nanos = f.as_uint64(i, 3);
+            o.sequence_number = f.as_uint64(i, 4);
+            out[i] = std::move(o);
+        } catch (const std::runtime_error& e) {
+            if (!errors) throw;
+            (*errors)[i] = e.what();
+        }
+    }
+    return out;
+}
+
+CommitOffset CommitManager::parse_commit_offset(const std::string& payload) {
+    return parse_commit_offsets_batch(std::vector<std::string>{payload}).front();
+}
+
 }  // namespace aeron_cluster

@@ -269,6 +269,63 @@ public:
 
 class ParsedBatch;
 
+// One member path of a JSON document for ParsedBatch::extract / extract_json_documents
+// (sbe_json_extract_batch): 1..4 decoded member names, raw bytes.  A std::string or a literal is
+// split at its dots ("message.message.order_id"); a list of names is taken as it is.
+struct JsonPath {
+    std::vector<std::string> names;
+    JsonPath(const char* dotted) : JsonPath(std::string(dotted)) {}
+    JsonPath(const std::string& dotted);
+    JsonPath(std::vector<std::string> parts) : names(std::move(parts)) {}
+};
+
+// sbe_json_extract_batch's outputs on the host (include/sbecodec.h: SBE_JX_*), with views into the
+// caller's bytes (valid while they are) and Value::asString's conversions.
+class JsonFields {
+public:
+    std::size_t size() const { return doc_.size(); }
+    std::size_t paths() const { return n_paths_; }
+    std::uint8_t doc(std::size_t i) const { return doc_[i]; }              // SBE_JX_OK .. SBE_JX_STACK
+    std::uint8_t root_kind(std::size_t i) const { return root_[i]; }
+    std::uint8_t kind(std::size_t i, std::size_t p) const { return kind_[i * n_paths_ + p]; }  // SBE_JX_MISSING .. ARRAY
+    // strings: the bytes between the quotes, escapes undecoded; numbers and literals: the token;
+    // containers: bracket to bracket; MISSING: empty
+    std::string_view token(std::size_t i, std::size_t p) const;
+    bool is_string(std::size_t i, std::size_t p) const;
+    // Value::asString (jsoncpp 1.9.5): the decoded string, a number as valueToString prints it,
+    // "true" / "false", "" for null and for a missing member (Value::get's null); a container throws
+    // std::runtime_error
+    std::string as_string(std::size_t i, std::size_t p) const;
+    // Value::asUInt64: null and a missing member 0, bools 0 / 1, integers in range exact, a real in
+    // [0, 2^64) truncated after strtod; a negative integer, a real outside that range, a string or
+    // a container throws std::runtime_error
+    std::uint64_t as_uint64(std::size_t i, std::size_t p) const;
+
+private:
+    friend struct JsonExtractAccess;
+    std::size_t n_paths_ = 0;
+    std::vector<std::uint8_t> doc_, root_, kind_;
+    std::vector<std::uint32_t> off_, len_;
+    std::vector<const char*> base_;  // record i's first byte
+};
+
+// The same for bare documents (dec == NULL): document i is docs[i]; views point into docs.
+JsonFields extract_json_documents(const std::vector<std::string>& docs, const std::vector<JsonPath>& paths);
+
+// What the reference's subscriber reads out of an Order message
+// (examples/pubsub_reconnect_test.cpp:576-620): message.message.client_order_id (else
+// message.message.order_details.client_order_id; with a non-object message.message the older
+// message.order_details.client_order_id), message.message.order_id, and the top-level uuid for an
+// empty order_id; only strings count.  Records the example does not look at (neither
+// is_order_message() nor a CREATE_ORDER topic message), an empty payload, a parse failure and
+// everything that throws there (a root that is neither an object nor null, the stack limit) give
+// two empty strings, as its catch (...) does.
+struct OrderIds {
+    std::string client_order_id, order_id;
+};
+std::vector<OrderIds> extract_order_ids(const ParsedBatch& batch);
+OrderIds extract_order_ids(const ParseResult& result);
+
 class MessageParser {
 public:
     // src/sbe_encoder.cpp:513-551 (never throws; success = false + error_message)
@@ -326,6 +383,10 @@ public:
     // Calls fn(i, result(i)) in record order on the calling thread; the ParseResults of each
     // 4096-record block are built on the host threads first.
     void for_each(const std::function<void(std::size_t, const ParseResult&)>& fn) const;
+    // The JSON members at `paths` of every TopicMessage's payload (view 3) or headers (view 4), read
+    // on the device as Json::parseFromStream with builder defaults reads them
+    // (sbe_json_extract_batch); select: null, or n bytes, 0 skips the record.
+    JsonFields extract(const std::vector<JsonPath>& paths, int view = 3, const std::uint8_t* select = nullptr) const;
 
 private:
     friend class MessageParser;
@@ -524,8 +585,18 @@ public:
     // src/commit_manager.cpp:197-209: the jsoncpp text of an offset, indentation "" (keys sorted, no
     // white space): {"action":"COMMIT_OFFSET","messageIdentifier":..,"message_id":..,
     // "sequence_number":..,"timestamp_nanos":..,"topic":..}.  Host-only code, as Order::validate.
-    // (parse_commit_offset needs a tree-building reader and stays out.)
     static std::string serialize_commit_offset(const CommitOffset& offset);
+    // src/commit_manager.cpp:177-195: topic, message_identifier and message_id through asString,
+    // timestamp_nanos and sequence_number through asUInt64, absent members "" / 0; the document is
+    // read on the device (five root paths of sbe_json_extract_batch).  A parse failure throws
+    // std::runtime_error whose text begins "Failed to parse commit offset JSON: " (jsoncpp's
+    // formatted error list behind the prefix is not reproduced); a root that is neither an object
+    // nor null, and a member asString / asUInt64 cannot convert, throw std::runtime_error too.
+    static CommitOffset parse_commit_offset(const std::string& payload);
+    // One launch for all: with `errors` a document that throws leaves a default CommitOffset and
+    // its message in (*errors)[i] ("" for the others); without, the first such document throws.
+    static std::vector<CommitOffset> parse_commit_offsets_batch(const std::vector<std::string>& payloads,
+                                                                std::vector<std::string>* errors = nullptr);
     // src/commit_manager.cpp:134-175, the unknown-topic branch of build_commit_offset_message on
     // the host, without a GPU: the TopicMessage {16,1,1,1} on "_subscriptions" of type
     // "COMMIT_OFFSET" with uuid "commit_offset_" + client_id + "_" + clock() and the text above as

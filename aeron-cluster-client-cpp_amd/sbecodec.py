@@ -127,6 +127,16 @@ class _AckOut(ctypes.Structure):
     _fields_ = [("code", ctypes.c_void_p), ("base_ns", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
 
 
+class _JsonPaths(ctypes.Structure):
+    _fields_ = [("n_paths", ctypes.c_uint32), ("depth", ctypes.c_void_p), ("names", ctypes.c_void_p),
+                ("name_off", ctypes.c_void_p)]
+
+
+class _JsonOut(ctypes.Structure):
+    _fields_ = [("doc", ctypes.c_void_p), ("root_kind", ctypes.c_void_p), ("kind", ctypes.c_void_p),
+                ("off", ctypes.c_void_p), ("len", ctypes.c_void_p)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise SbeError(f"{LIB_PATH} is missing: build it with `make -C aeron-cluster-client-cpp_amd` "
@@ -192,6 +202,14 @@ def _load():
                                          ctypes.POINTER(_Decoded), ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_uint32, ctypes.POINTER(_CommitOut), ctypes.c_void_p,
                                          ctypes.c_size_t, ctypes.c_void_p]
+    if hasattr(lib, "sbe_json_extract_batch"):
+        lib.sbe_json_extract_workspace_size.restype = ctypes.c_size_t
+        lib.sbe_json_extract_workspace_size.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+        lib.sbe_json_extract_batch.restype = ctypes.c_int
+        lib.sbe_json_extract_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.POINTER(_Decoded), ctypes.c_uint32, ctypes.c_void_p,
+                                               ctypes.POINTER(_JsonPaths), ctypes.POINTER(_JsonOut), ctypes.c_void_p,
+                                               ctypes.c_size_t, ctypes.c_void_p]
     if hasattr(lib, "sbe_emit_commit_offsets"):
         lib.sbe_commit_emit_workspace_size.restype = ctypes.c_size_t
         lib.sbe_commit_emit_workspace_size.argtypes = [ctypes.c_uint64]
@@ -653,6 +671,87 @@ def classify_commits(data, rec_off, dec: Decoded, topics, out: CommitPlan | None
     _check(rc, "sbe_classify_commits")
     if n < out.cm.numel():
         out = CommitPlan(*(getattr(out, f)[:n] for f, _ in _COMMIT_KEYS[:6]), out.last, out.count)
+    return out
+
+
+# sbe_json_extract_batch: document codes, value kinds and the path table's caps (include/sbecodec.h)
+JX_OK, JX_NOT_SELECTED, JX_EMPTY, JX_FAILED, JX_STACK = range(5)
+JX_MISSING, JX_STRING, JX_STRING_ESC, JX_NUMBER, JX_TRUE, JX_FALSE, JX_NULL, JX_OBJECT, JX_ARRAY = range(9)
+JSON_MAX_PATHS, JSON_MAX_DEPTH, JSON_MAX_NAME, JSON_NAME_BYTES = 16, 4, 64, 1024
+VIEW_PAYLOAD, VIEW_HEADERS = 3, 4
+_JSON_KEYS = (("doc", "uint8"), ("root_kind", "uint8"), ("kind", "uint8"), ("off", "uint32"), ("len", "uint32"))
+# the members examples/pubsub_reconnect_test.cpp:576-620 looks at to name the Order of a message
+ORDER_ID_PATHS = ("message", "message.message", "message.message.client_order_id", "message.message.order_id",
+                  "message.message.order_details", "message.message.order_details.client_order_id",
+                  "message.order_details", "message.order_details.client_order_id", "uuid")
+
+
+@dataclass
+class JsonFields:
+    doc: torch.Tensor        # uint8 [n]     JX_OK .. JX_STACK
+    root_kind: torch.Tensor  # uint8 [n]     JX_MISSING .. JX_ARRAY
+    kind: torch.Tensor       # uint8 [n, P]  JX_MISSING .. JX_ARRAY
+    off: torch.Tensor        # int32 [n, P]  (u32) relative to the record start
+    len: torch.Tensor        # int32 [n, P]  (u32)
+
+    def numpy(self):
+        import numpy as np
+        return {k: getattr(self, k).cpu().numpy().view(getattr(np, t)) for k, t in _JSON_KEYS}
+
+
+def json_path_table(paths):
+    """The host arrays of sbe_json_paths: (n_paths, depth uint8, names uint8, name_off uint32).
+    A path is a dotted str or a sequence of names (str or bytes; bytes are taken as they are)."""
+    import numpy as np
+    flat, depth = [], []
+    for p in paths:
+        parts = p.split(".") if isinstance(p, str) else list(p)
+        parts = [q.encode() if isinstance(q, str) else bytes(q) for q in parts]
+        depth.append(len(parts))
+        flat += parts
+    if any(d > 255 for d in depth):
+        raise SbeError("a JSON path holds more than 255 names")
+    off = np.zeros(len(flat) + 1, np.uint32)
+    off[1:] = np.cumsum([len(q) for q in flat])
+    names = np.frombuffer(b"".join(flat) + b"\0", np.uint8).copy()  # never empty
+    return len(depth), np.asarray(depth, np.uint8), names, off
+
+
+def extract_json(data, rec_off, dec, paths, view=None, select=None, out: JsonFields | None = None,
+                 stream=None) -> JsonFields:
+    """The JSON members at `paths` of every document of a batch, read as Json::parseFromStream with
+    builder defaults reads them (what a consumer's callback does with result.payload,
+    examples/pubsub_reconnect_test.cpp:576-620).  dec: the Decoded of a parse-mode decode_batch on
+    the same data / rec_off, and view VIEW_PAYLOAD (default) or VIEW_HEADERS; or None, when every
+    record is a bare document.  select: optional uint8 [n], 0 skips the record.  paths: see
+    json_path_table (or its result).  Returns doc / root_kind per record and kind / off / len per
+    record and path; the ranges are relative to the record start, the host converts the tokens."""
+    data = _dev(data, torch.uint8, "data")
+    rec_off = _dev(rec_off, torch.int64, "rec_off")
+    select = _dev(select, torch.uint8, "select")
+    n = int(rec_off.numel()) - 1
+    dev = data.device
+    if view is None:
+        view = 0 if dec is None else VIEW_PAYLOAD
+    table = paths if isinstance(paths, tuple) and len(paths) == 4 and isinstance(paths[0], int) else json_path_table(paths)
+    P, depth, names, name_off = table
+    if select is not None and select.numel() < n:
+        raise SbeError("select holds fewer than n entries")
+    if out is None:
+        m = max(n, 1)
+        out = JsonFields(torch.empty(m, dtype=torch.uint8, device=dev), torch.empty(m, dtype=torch.uint8, device=dev),
+                         torch.empty((m, max(P, 1)), dtype=torch.uint8, device=dev),
+                         torch.empty((m, max(P, 1)), dtype=torch.int32, device=dev),
+                         torch.empty((m, max(P, 1)), dtype=torch.int32, device=dev))
+    ps = _JsonPaths(P, depth.ctypes.data, names.ctypes.data, name_off.ctypes.data)
+    o = _JsonOut(*(getattr(out, f).data_ptr() for f, _ in _JSON_KEYS))
+    d = None if dec is None else ctypes.byref(
+        _Decoded(*(getattr(dec, f).data_ptr() for f in ("status", "flags", "hdr", "ts", "view_off", "view_len"))))
+    rc = lib().sbe_json_extract_batch(_ptr(data), _ptr(rec_off), n, d, view, _ptr(select), ctypes.byref(ps),
+                                      ctypes.byref(o), None, 0, _stream(stream))
+    _check(rc, "sbe_json_extract_batch")
+    if n < out.doc.numel():
+        out = JsonFields(*(getattr(out, f)[:n] for f, _ in _JSON_KEYS))
     return out
 
 

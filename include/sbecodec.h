@@ -72,6 +72,11 @@
  *                                  ack callback wired at :1648: find / erase in inflight_ and the time
  *                                  the round trip is measured from (sbe_inflight_init, _rehash,
  *                                  _table_size, _workspace_size manage the device table)
+ * sbe_json_extract_batch()        what a consumer's callback reads out of result.payload: the
+ *                                  Json::parseFromStream + isMember / operator[] lookups of
+ *                                  examples/pubsub_reconnect_test.cpp:576-620 (again :1142-1160) and of
+ *                                  CommitManager::parse_commit_offset src/commit_manager.cpp:177-195,
+ *                                  for a table of member paths over a whole batch
  * sbe_serve_*()                   the same encoders / decoders for small batches (one record per
  *                                  call, as the reference's per-message API is used: parse_message per
  *                                  fragment src/cluster_client.cpp:1185, publish_topic per message)
@@ -408,6 +413,79 @@ size_t sbe_commit_workspace_size(uint64_t n, uint32_t k);
 int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
                          const uint8_t* topic_arena, const uint32_t* topic_off, uint32_t k,
                          const sbe_commit_out* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ============================== JSON members by path ============================== */
+/* The members a consumer reads out of a decoded JSON document (the payload or the headers of a
+ * TopicMessage, or a bare document), for a caller-given table of member paths and every record of
+ * a batch in one launch.  A path is 1..SBE_JSON_MAX_DEPTH member names, e.g. message / message /
+ * order_details / client_order_id; a table holds 1..SBE_JSON_MAX_PATHS distinct paths.  Names are
+ * the decoded member names: raw bytes, 1..SBE_JSON_MAX_NAME each, SBE_JSON_NAME_BYTES in all.
+ *
+ * The document is parsed as Json::parseFromStream / CharReader::parse with CharReaderBuilder
+ * defaults parse it (jsoncpp 1.9.5; the reader sbe_eval_sequence_numbers and sbe_classify_commits
+ * use): comments and trailing commas allowed, a BOM skipped, a NUL ends the stream, content after
+ * the root ignored, stack limit 1000, a later duplicate key replaces the earlier value.  doc[i]: */
+#define SBE_JX_OK 0u            /* the root parsed; root_kind[i] says what it is */
+#define SBE_JX_NOT_SELECTED 1u  /* select[i] == 0, or (with descriptors) the record is not an SBE_ST_TM */
+#define SBE_JX_EMPTY 2u         /* a zero-byte document (every reference caller tests .empty() first); also
+                                   view 4 under SBE_FL_HEADERS_E100 */
+#define SBE_JX_FAILED 3u        /* the parse returns false */
+#define SBE_JX_STACK 4u         /* the reader throws "Exceeded stackLimit in readValue()" */
+/* Everything but SBE_JX_OK leaves root_kind and every path SBE_JX_MISSING.
+ * kind[i][p], per record and path (1..6 are the SBE_TOPIC_KIND_* values): */
+#define SBE_JX_MISSING 0u
+#define SBE_JX_STRING 1u        /* no backslash: the range is the string verbatim */
+#define SBE_JX_STRING_ESC 2u    /* the host decodes the escapes */
+#define SBE_JX_NUMBER 3u        /* a token the reader accepted as a number; the host converts it */
+#define SBE_JX_TRUE 4u
+#define SBE_JX_FALSE 5u
+#define SBE_JX_NULL 6u
+#define SBE_JX_OBJECT 7u
+#define SBE_JX_ARRAY 8u
+/* off / len are relative to the record's first byte.  Strings: the bytes between the quotes;
+ * numbers and literals: the token; containers: from the opening bracket through the closing one
+ * (jsoncpp's getOffsetStart() .. getOffsetLimit()); MISSING: 0, 0.  A path resolves through
+ * objects only: when a prefix is missing or is not an object the path is MISSING (a caller who
+ * must tell the two apart adds the prefix as a path of its own).  The last of several equal keys
+ * wins at every level, also when it replaces an object by a scalar; member names are compared
+ * after decodeString (a name spelled with escapes matches its decoded form).  No numeric values are
+ * produced: number tokens are validated as the reader validates them and returned as ranges. */
+#define SBE_JSON_MAX_PATHS 16u
+#define SBE_JSON_MAX_DEPTH 4u
+#define SBE_JSON_MAX_NAME 64u
+#define SBE_JSON_NAME_BYTES 1024u
+
+typedef struct sbe_json_paths { /* host memory, read during the call only */
+    uint32_t n_paths;
+    const uint8_t* depth;     /* [n_paths] names per path */
+    const uint8_t* names;     /* the names of path 0, then of path 1, ..., back to back */
+    const uint32_t* name_off; /* [sum of depth + 1] name j is names[name_off[j] .. name_off[j+1]) */
+} sbe_json_paths;
+
+typedef struct sbe_json_out { /* device arrays; P = n_paths */
+    uint8_t* doc;       /* [n] SBE_JX_OK .. SBE_JX_STACK */
+    uint8_t* root_kind; /* [n] */
+    uint8_t* kind;      /* [n][P] */
+    uint32_t* off;      /* [n][P] */
+    uint32_t* len;      /* [n][P] */
+} sbe_json_out;
+
+/* Workspace bytes sbe_json_extract_batch needs (0: none; workspace may then be NULL). */
+size_t sbe_json_extract_workspace_size(uint64_t n, uint32_t n_paths);
+
+/* Extract the paths from n documents.  dec == NULL: record i, in[rec_off[i] .. rec_off[i+1]), is
+ * the document itself, and view must be 0.  With dec (the outputs of
+ * sbe_decode_batch(SBE_DEC_PARSE_MESSAGE) on the same in / rec_off) the document is view 3
+ * (payload) or view 4 (headers) of every SBE_ST_TM record, kept inside its record whatever the
+ * descriptors say.  select: NULL, or a device u8 [n] (0: the record is skipped).  The path table
+ * travels in the launch arguments: the call reads no device table and makes no copy.  One launch
+ * on `stream`; every element i < n of the five output arrays is written.  n == 0 is SBE_OK with
+ * no launch.  SBE_EINVAL (before any launch, nothing written): a null pointer, a path table
+ * outside the limits above, an empty name, the same path twice, a view that does not go with dec,
+ * rec_off not 8-byte or a u32 array not 4-byte aligned. */
+int sbe_json_extract_batch(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                           uint32_t view, const uint8_t* select, const sbe_json_paths* paths,
+                           sbe_json_out* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ============================== commit-offset frames ============================== */
 /* The second half of ClusterClient::commit_message (src/cluster_client.cpp:626-633) for a batch

@@ -19,6 +19,9 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
                          same run sbe_encode_lite_batch on a pre-gathered arena of the same ids
   commit_fallback        the commit_emit batch with a table whose entries all have id 0 → session-framed
                          JSON COMMIT_OFFSET TopicMessages (sbe_emit_commit_offsets_ex with a fallback)
+  json_extract           1 M decoded fixed-256 Orders, the nine order-id member paths read out of every
+                         payload (sbe_json_extract_batch), flat and nested payloads, and in the same run
+                         sbe_classify_commits on the same buffers (same staging, no record parsed)
   ack_correlate          1 M "pub_<nanos>" uuids remembered in a 2 M-slot in-flight table, then 1 M full
                          acks (about 10 % unknown ids, 1 % repeated ids) decoded on-egress and matched;
                          remember, match and the decode of the same ack batch timed in the same run, and
@@ -507,6 +510,58 @@ def row_autocommit(steps, warmup):
         torch.cuda.empty_cache()
 
 
+def row_json_extract(steps, warmup):
+    """sbe_json_extract_batch after a parse_message decode of 1 M fixed-256 Orders, the nine
+    order-id paths of examples/pubsub_reconnect_test.cpp:576-620 over the payloads: the suite's flat
+    payload (every record is parsed whole, no path is found) and a nested payload of the same 143
+    bytes in Order::to_json's shape (five of the nine paths are found).  Every selected record is
+    parsed, so beside each the same run times sbe_classify_commits on the same buffers: the same
+    staging, but no record of these batches reaches its reader.  Bytes: the payload read, 18 B of
+    descriptors (rec_off 8, status 1, flags 1, one view offset and length 8) and 2 + 9 P B of
+    outputs a record."""
+    n = 1_000_000
+    arena, L, ts = T.fixed256_orders(n)
+    nested = (b'{"uuid":"cid_0123456789abcdefg","message":{"message":{"order_details":'
+              b'{"client_order_id":"cid_0123456789abcdefg"}}}}')
+    assert len(nested) <= 143, len(nested)
+    hit_arena = arena.reshape(n, 222).copy()
+    hit_arena[:, 47:190] = np.frombuffer(nested.ljust(143), np.uint8)
+    paths = sbecodec.json_path_table(sbecodec.ORDER_ID_PATHS)
+    topics = [b"orders", b"order_request_topic", b"order_notification_topic"]
+    for name, ar in (("fixed256", arena), ("fixed256_nested", hit_arena.reshape(-1))):
+        data, off = T.oracle_encode(ar, L, ts)[:2]
+        d0, o0 = dev(data, torch.uint8), dev(np.asarray(off, np.uint64), torch.int64)
+        table = sbecodec.commit_topic_table(topics, "cuda")
+
+        def make(k):
+            d, o = d0.clone(), o0.clone()
+            dec = sbecodec.decode_batch(d, o, sbecodec.DEC_PARSE_MESSAGE, out=sbecodec.alloc_decoded(n, "cuda"),
+                                        in_bytes=data.size)
+            return d, o, dec, sbecodec.extract_json(d, o, dec, paths), sbecodec.classify_commits(d, o, dec, table)
+        R = Rot(make)
+        torch.cuda.synchronize()
+        dec0, got0 = R.sets[0][2], R.sets[0][3].numpy()
+        pbytes = int(dec0.view_len[:n, 3].to(torch.int64).sum().item())
+        found = (got0["kind"] != 0).sum(axis=0).tolist()
+
+        def fn():
+            d, o, dec, out, _ = R.next()
+            sbecodec.extract_json(d, o, dec, paths, out=out)
+        ms = _event_ms(fn, steps, warmup)
+
+        def cfn():
+            d, o, dec, _, plan = R.next()
+            sbecodec.classify_commits(d, o, dec, table, out=plan)
+        cms = _event_ms(cfn, steps, warmup)
+        line(f"json_extract_{name}", n, ms * 1e-3,
+             {"sbe_json_extract_batch (9 order-id paths)": (ms, pbytes + (18 + 2 + 9 * 9) * n),
+              "sbe_classify_commits (same buffers, same run)": (cms, pbytes + 32 * n + (42 + 15) * n)})
+        print(json.dumps({"row": f"json_extract_{name}", "payload_bytes": pbytes, "payload_GBps": pbytes / (ms * 1e-3) / 1e9,
+                          "doc_counts": np.bincount(got0["doc"], minlength=5).tolist(), "found_per_path": found}), flush=True)
+        del R
+        torch.cuda.empty_cache()
+
+
 def row_commit_emit(steps, warmup):
     """sbe_emit_commit_offsets over 1 M decoded and classified fixed-256 Orders whose headers all
     carry a known topic (every record emits a session-framed CommitOffsetLite; short identifiers),
@@ -735,7 +790,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,commit_emit,commit_fallback,ack_correlate")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,commit_emit,commit_fallback,ack_correlate")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -764,6 +819,8 @@ def main():
             row_materialize(args.steps, args.warmup)
         elif r == "autocommit":
             row_autocommit(args.steps, args.warmup)
+        elif r == "json_extract":
+            row_json_extract(args.steps, args.warmup)
         elif r == "commit_emit":
             row_commit_emit(args.steps, args.warmup)
         elif r == "commit_fallback":
