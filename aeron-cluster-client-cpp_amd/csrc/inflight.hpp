@@ -93,16 +93,11 @@ __device__ __forceinline__ uint64_t inf_hash(const InfKey& k) {
 }
 __device__ __forceinline__ uint32_t inf_tag(uint64_t h, uint32_t tag_bits) { return (uint32_t)(h >> 34) & ((1u << tag_bits) - 1u); }
 
-#ifndef SBE_INF_TRUST_TAG  // mutation builds only: an equal tag stands for equal bytes
-#define SBE_INF_TRUST_TAG 0
-#endif
 __device__ __forceinline__ bool inf_key_eq(const InfKey& a, const InfKey& b) {
-    if (SBE_INF_TRUST_TAG) return true;
     return a.len == b.len && a.w[0] == b.w[0] && a.w[1] == b.w[1] && a.w[2] == b.w[2] && a.w[3] == b.w[3] &&
            a.w[4] == b.w[4];
 }
 __device__ __forceinline__ bool inf_slot_eq(const InfSlot* s, const InfKey& k) {
-    if (SBE_INF_TRUST_TAG) return true;
     return s->len == k.len && s->key[0] == k.w[0] && s->key[1] == k.w[1] && s->key[2] == k.w[2] && s->key[3] == k.w[3] &&
            s->key[4] == k.w[4];
 }

@@ -208,14 +208,7 @@ __device__ inline uint32_t nul16(const uint4& v) {  // bit k set iff byte k of t
     return nul4(v.x) | (nul4(v.y) << 4) | (nul4(v.z) << 8) | (nul4(v.w) << 12);
 }
 
-#ifndef SBE_OJ_INLINE  // A/B builds: 1 = the string and number helpers inlined into the kernels
-#define SBE_OJ_INLINE 0
-#endif
-#if SBE_OJ_INLINE
-#define OJ_HELPER __forceinline__
-#else
-#define OJ_HELPER __noinline__
-#endif
+#define OJ_HELPER __noinline__  // the string and number helpers stay out of line
 
 // jsoncpp valueToQuotedStringN(str, len, emitUTF8 = false)
 // Out-of-line helpers take the sink by value and return it: a sink passed by reference lives in
@@ -958,14 +951,12 @@ __global__ __launch_bounds__(kScanThreads) void order_json_scan_blocks(uint64_t*
 // coalesced 16-byte loads issued back to back, and sizes the texts from there, instead of each
 // lane walking its strings with a chain of dependent HBM loads (the launch's latency bound).  A
 // range larger than the wave's LDS share is read from HBM as before.
-#ifndef SBE_OJ_MSTR  // LDS bytes per wave for the staged strings (0: never staged)
+#ifndef SBE_OJ_MSTR  // LDS bytes per wave for the staged strings
 #define SBE_OJ_MSTR 10240
 #endif
-// A/B builds: 0 = headers texts (3 of the 8 strings) sized from HBM, not staged: measured slower
-// (row 0.560 -> 0.580 ms, profiles/r05_ab_ojhstage.log), so the headers launch stages all 8 as well
-#ifndef SBE_OJ_HSTAGE
-#define SBE_OJ_HSTAGE 1
-#endif
+static_assert(SBE_OJ_MSTR > 0, "the sizing launches stage their strings");
+// The headers launch stages all 8 strings as well: its texts (3 of the 8 strings) sized from HBM
+// measured slower (row 0.560 -> 0.580 ms, profiles/r05_ab_ojhstage.log)
 // The packed-arena staging of a sizing launch: the strings of the wave's Orders [i0, i0 + 64) are
 // one contiguous arena range [g0, end) (g0 rounded down to 16); when it fits kBytes the wave copies
 // it into its LDS share sb with coalesced 16-byte loads and returns true (sb[0] = arena[g0]).
@@ -1008,15 +999,12 @@ __global__ __launch_bounds__(kBlock) void order_json_measure(JsonArgs a) {
             tot += l[j];
         }
     uint64_t len = 0, total;
-    bool done = false;
     if (!a.str_off) {  // uniform over the launch
         const uint64_t base = a.blk_str[blockIdx.x] + block_excl_scan(tot, wtot, lane, wv, total);
         if (live) a.str_base[i] = base;
-#if SBE_OJ_MSTR > 0
-        constexpr bool kStage = kWhat != SBE_JSON_PUBLISH_HEADERS || SBE_OJ_HSTAGE;
-        __shared__ __attribute__((aligned(16))) uint8_t sbuf[kBlock / kWave][kStage ? SBE_OJ_MSTR : 16];
+        __shared__ __attribute__((aligned(16))) uint8_t sbuf[kBlock / kWave][SBE_OJ_MSTR];
         uint64_t g0 = 0;
-        const bool staged = kStage && stage_wave_strings<(kStage ? SBE_OJ_MSTR : 0)>(a.arena, sbuf[wv], base, tot, a.n, i - lane, lane, g0);
+        const bool staged = stage_wave_strings<SBE_OJ_MSTR>(a.arena, sbuf[wv], base, tot, a.n, i - lane, lane, g0);
         __syncthreads();
         if (staged && live) {
             lr8* f[kFields];
@@ -1029,9 +1017,7 @@ __global__ __launch_bounds__(kBlock) void order_json_measure(JsonArgs a) {
             order_text<kWhat>(c, a, i, f, l);
             len = c.n;
         }
-        done = staged;
-#endif
-        if (!done && live) {
+        if (!staged && live) {
             gu8* f[kFields];
             uint64_t at = base;
             for (uint32_t j = 0; j < kFields; ++j) {

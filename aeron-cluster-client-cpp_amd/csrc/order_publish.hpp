@@ -158,7 +158,6 @@ __global__ __launch_bounds__(kBlock) void publish_measure(PubArgs a) {
     if (!a.j.str_off) {  // uniform over the launch
         base = a.j.blk_str[blockIdx.x] + block_excl_scan(tot, wtot, lane, wv, total);
         if (live) a.j.str_base[i] = base;
-#if SBE_OJ_MSTR > 0
         __shared__ __attribute__((aligned(16))) uint8_t sbuf[kBlock / kWave][SBE_OJ_MSTR];
         uint64_t g0 = 0;
         const bool staged = stage_wave_strings<SBE_OJ_MSTR>(a.j.arena, sbuf[wv], base, tot, a.j.n, i - lane, lane, g0);
@@ -173,7 +172,6 @@ __global__ __launch_bounds__(kBlock) void publish_measure(PubArgs a) {
             rec = size_one(a, i, f, l, chk_at);
         }
         done = staged;
-#endif
     }
     if (!done && live) {
         gu8* f[kFields];

@@ -268,15 +268,6 @@ struct Lay {
     static constexpr int32_t kBlk = kBlk_;
     static constexpr int kNF = kNF_;
     static constexpr bool kTM = kTM_;                 // TopicMessage block (timestamp default, truncation)
-    // staged-input loads nontemporal: the input is read once.  On inputs that rotate over three
-    // buffer sets (no step finds its input in the 256 MB MALL, as streaming data would not) they
-    // read fixed-256 96.0 -> 94.2 us, config 4 723.3 -> 716.6, OrderRequestLite 146.3 -> 143.8,
-    // session frames 137.7 -> 137.2 (profiles/r06_ab_ntl_rot.log); only a batch re-read every step
-    // (rounds 1-5's bench) prefers the default policy, whose lines the MALL keeps (86.6 vs 93.9 us)
-#ifndef SBE_PACK_NTL  // A/B builds: 0 = never, 1 = TopicMessage / OrderRequestLite, 2 = always
-#define SBE_PACK_NTL 2
-#endif
-    static constexpr bool kNtIn = SBE_PACK_NTL == 2 || (SBE_PACK_NTL == 1 && (kTM_ ? kPre_ == 0 : kNF_ == 3));
     static constexpr int32_t kLit = kPre + 8 + kBlk;  // literal prefix bytes (multiple of 4)
     static constexpr int32_t kS0 = kLit + 2;          // first string byte
     static constexpr int32_t kOvh = kLit + 2 * kNF;   // wire overhead
@@ -449,7 +440,6 @@ typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
-typedef __attribute__((address_space(3))) const u32x2 lds_cu32x2;
 typedef __attribute__((address_space(3))) u32x2 lds_u32x2;
 __device__ __forceinline__ void lds_store16(lds_u8* p, uint4 v) {
     u32x4 x;
@@ -815,17 +805,18 @@ __device__ __forceinline__ void stage_range(const TileSt& S, int32_t wrel, int l
 // Always kStageRegs loads (all lanes, offsets clamped into [swb, swb + nbytes); swb must be
 // readable for 16 bytes when nbytes == 0): the loop body's vector-memory operations are then
 // straight-line, so the compiler's vmcnt waits count them exactly instead of draining all.
-// kNt: nontemporal loads (Lay::kNtIn: the input is read once and not from this kernel's caches again)
-template <bool kNt>
+// The loads are nontemporal: the input is read once.  On inputs that rotate over three buffer sets
+// (no step finds its input in the 256 MB MALL, as streaming data would not) they read fixed-256
+// 96.0 -> 94.2 us, config 4 723.3 -> 716.6, OrderRequestLite 146.3 -> 143.8, session frames
+// 137.7 -> 137.2 (profiles/r06_ab_ntl_rot.log); only a batch re-read every step (rounds 1-5's
+// bench) prefers the default policy, whose lines the MALL keeps (86.6 vs 93.9 us).
 __device__ __forceinline__ void stage_issue(uintptr_t swb, int32_t nbytes, int lane, uint4 (&I)[kStageRegs]) {
     g_u32x4* const base = reinterpret_cast<g_u32x4*>(swb);  // uniform base + 32-bit lane offsets
     const uint32_t last = nbytes >= 16 ? (uint32_t)(nbytes - 16) >> 4 : 0u;
 #pragma unroll
     for (int k = 0; k < kStageRegs; ++k) {
         const uint32_t ch = lane + kWave * k;
-        u32x4 v;
-        if constexpr (kNt) v = __builtin_nontemporal_load(base + (ch < last ? ch : last));
-        else v = base[ch < last ? ch : last];
+        const u32x4 v = __builtin_nontemporal_load(base + (ch < last ? ch : last));
         I[k] = make_uint4(v.x, v.y, v.z, v.w);
     }
 }
@@ -1066,53 +1057,18 @@ __device__ __forceinline__ RecEnt rec_load(lds_i32* rt, int32_t r) {
 }
 
 // The five dwords i .. i+4 of the staged input (a 16-byte chunk at any byte alignment inside them).
-// SBE_CHUNK_B64: as three ds_read_b64 at the 8-byte aligned dword i & ~1 and one select per dword
-// (banks (a/4) mod 64 for ds_read_b64, against (a/4) mod 32 for ds_read_b32: lanes whose chunks lie
-// 128 B apart, the two lanes of a 256-B record, or a rebalanced window's runs of 16 T bytes, stop
-// sharing banks); else five ds_read_b32.  i <= imax - 1 (the b64 form reads one dword further).
-#ifndef SBE_CHUNK_B64
-#define SBE_CHUNK_B64 0
-#endif
+// As five ds_read_b32: three ds_read_b64 and a select per dword read the fixed-256 pack 94.1 ->
+// 95.3 us and config 4 722.1 -> 736.1 (profiles/r04_ab_ackfast_b64_rebal.log); one unaligned
+// ds_read_b128, whose misaligned access the LDS replays, was slower too.
 __device__ __forceinline__ void lds_dw5(lds_cu8* inb, int32_t i, uint32_t (&d)[5]) {
-    if (SBE_CHUNK_B64) {
-        const lds_cu32x2* q = reinterpret_cast<lds_cu32x2*>(reinterpret_cast<lds_cu32*>(inb) + (i & ~1));
-        const u32x2 a = q[0], b = q[1], c = q[2];
-        const bool odd = (i & 1) != 0;
-        d[0] = odd ? a.y : a.x;
-        d[1] = odd ? b.x : a.y;
-        d[2] = odd ? b.y : b.x;
-        d[3] = odd ? c.x : b.y;
-        d[4] = odd ? c.y : c.x;
-    } else {
-        lds_cu32* q = reinterpret_cast<lds_cu32*>(inb) + i;
+    lds_cu32* q = reinterpret_cast<lds_cu32*>(inb) + i;
 #pragma unroll
-        for (int j = 0; j < 5; ++j) d[j] = q[j];
-    }
+    for (int j = 0; j < 5; ++j) d[j] = q[j];
 }
 
-// SBE_CHUNK_UA (A/B builds): a chunk at any staged byte position as ONE unaligned ds_read_b128
-// (the LDS replays the misaligned access) instead of five dword reads and four v_alignbyte.
-// Fewer instructions, but the replays cost more: fixed-256 pack 94.7 -> 99.0 us, config 4 706.3
-// -> 709.3, session 125.6 -> 128.6, OrderRequestLite 144.6 -> 150.2 (profiles/r06_ab_ua.log).
-#ifndef SBE_CHUNK_UA
-#define SBE_CHUNK_UA 0
-#endif
-typedef uint32_t u32x4_ua1 __attribute__((ext_vector_type(4), aligned(1)));
-typedef __attribute__((address_space(3))) const u32x4_ua1 lds_cu32x4_ua;
-// the 16 bytes at staged byte u, u clamped to [-kInSlack, 4 * imax] (a clamped read only ever feeds
-// don't-care bytes; 4 * imax + 16 <= the dword form's last byte read)
-__device__ __forceinline__ u32x4 lds_chunk_ua(lds_cu8* inb, int32_t u, int32_t imax) {
-    const int32_t lo = -kInSlack, hi = 4 * imax;
-    u = u < lo ? lo : (u > hi ? hi : u);
-    const u32x4_ua1 x = *reinterpret_cast<lds_cu32x4_ua*>(inb + u);
-    u32x4 v;
-    v.x = x.x; v.y = x.y; v.z = x.z; v.w = x.w;
-    return v;
-}
 // the 16 bytes at staged-input position u (any alignment); the base is clamped into the array
 // (a clamped read only ever feeds don't-care bytes)
 __device__ __forceinline__ u32x4 chunk_lds(lds_cu8* inb, int32_t u, int32_t imax) {
-    if (SBE_CHUNK_UA) return lds_chunk_ua(inb, u, imax);
     int32_t i = u >> 2;
     i = i < -kInSlack / 4 ? -kInSlack / 4 : (i > imax ? imax : i);
     const uint32_t sh = (uint32_t)u & 3u;
@@ -1281,31 +1237,19 @@ __device__ __forceinline__ void chunk_pass(lds_u8* wout, lds_cu8* inb, lds_i32* 
         }
         u[k] = p - E.sh0 - 2 * zone_of(E, p - E.rw);
     }
-#if SBE_CHUNK_UA
-    u32x4 w[kCpl];
-#else
     uint32_t d[kCpl][5];
-#endif
 #pragma unroll
     for (int k = 0; k < kCpl; ++k) {
         if (k >= kk) break;
-#if SBE_CHUNK_UA
-        w[k] = lds_chunk_ua(inb, u[k], imax - 1);
-#else
         int32_t i = u[k] >> 2;
         i = i < -kInSlack / 4 ? -kInSlack / 4 : (i > imax - 1 ? imax - 1 : i);
         lds_dw5(inb, i, d[k]);
-#endif
     }
     lds_u8* const wl = wout + lb + (lb >> 8) * kRowPad;  // padded rows never split a lane
 #pragma unroll
     for (int k = 0; k < kCpl; ++k) {
         if (k >= kk) break;
-#if SBE_CHUNK_UA
-        const u32x4 v = w[k];
-#else
         const u32x4 v = align4(d[k][0], d[k][1], d[k][2], d[k][3], d[k][4], (uint32_t)u[k] & 3u);
-#endif
         if (lb + 16 * k < wlen) *reinterpret_cast<lds_u32x4*>(wl + 16 * k) = v;
     }
 }
@@ -1672,32 +1616,20 @@ __device__ __forceinline__ bool compose_records(const EncArgs& ea, lds_u8* wout,
     auto group = [&](auto kGc, int32_t i0) {
         constexpr int kG = decltype(kGc)::value;
         int32_t u[kG];
-#if SBE_CHUNK_UA
-        u32x4 w[kG];
-#else
         uint32_t d[kG][5];
-#endif
 #pragma unroll
         for (int k = 0; k < kG; ++k) {
             const int32_t X = 16 * (cb + i0 + k) - brw;
             const int32_t f = (X >= bz1) + (X >= bz2) + (X >= bz3) + (X >= bz4);
             u[k] = bsrc0 + X - 2 * f;
-#if SBE_CHUNK_UA
-            w[k] = lds_chunk_ua(inb, u[k], imax - 1);
-#else
             int32_t i = u[k] >> 2;
             i = i < -kInSlack / 4 ? -kInSlack / 4 : (i > imax - 1 ? imax - 1 : i);
             lds_dw5(inb, i, d[k]);
-#endif
         }
 #pragma unroll
         for (int k = 0; k < kG; ++k) {
             // the zone of the chunk's first byte; string starts inside it: zone_fixup
-#if SBE_CHUNK_UA
-            const u32x4 v = w[k];
-#else
             const u32x4 v = align4(d[k][0], d[k][1], d[k][2], d[k][3], d[k][4], (uint32_t)u[k] & 3u);
-#endif
             if (i0 + k < n_mine) {
                 const int32_t p = 16 * (cb + i0 + k);
                 *reinterpret_cast<lds_u32x4*>(wout + wout_addr(p)) = v;
@@ -1877,7 +1809,7 @@ __device__ __forceinline__ void enc_pack_run(const EncArgs& a, uint64_t first, u
     bool fast = kPacked && !S.wrapped && !tile_big<LY>(S, lane);
     if (fast) W = tile_window<LY>(S, 0, lane, sink);
     if (kPacked) {
-        stage_issue<LY::kNtIn>(W.swb, W.nb, lane, I);
+        stage_issue(W.swb, W.nb, lane, I);
         stage_write(win_in, W.nb, lane, I);
     }
     uint64_t tn = t + G;
@@ -1904,7 +1836,7 @@ __device__ __forceinline__ void enc_pack_run(const EncArgs& a, uint64_t first, u
             fast_n = kPacked && !Sn.wrapped && !tile_big<LY>(Sn, lane);
             if (fast_n) Wn = tile_window<LY>(Sn, 0, lane, sink);
         }
-        if (have_next && kPacked) stage_issue<LY::kNtIn>(Wn.swb, Wn.nb, lane, I);
+        if (have_next && kPacked) stage_issue(Wn.swb, Wn.nb, lane, I);
         ph.lap(0);
         // current window (fast) or the whole tile window by window
         if (fast) {
@@ -1977,14 +1909,11 @@ __device__ __forceinline__ void enc_pack_run(const EncArgs& a, uint64_t first, u
 // (Tile-aligned steps leave a tile's last window part full: a 32-record tile of ~380-B records is
 // a full 8 KiB window and a ~4 KiB one, and a window costs about the same whatever it holds.)  The
 // records after the window start the next step; their lengths are loaded one step ahead, like the
-// tiles'.  Chunks rather than one contiguous range per workgroup: the windows in flight at once
-// then lie CT tiles apart, not n / G records (contiguous ranges measured the fixed-256 pack 10 %
-// slower, profiles/r04_ab_vt.log; chunks did not recover it, see SBE_PACK_VT).  A virtual tile
-// the fast path cannot take (a record longer than a window, gather mode, a PUBLISH_TOPIC length
-// wrap) is written whole, window by window.
-#ifndef SBE_VT_CHUNK  // tiles per chunk (0: one contiguous range per workgroup, the batch kernel's)
-#define SBE_VT_CHUNK 0
-#endif
+// tiles'.  CT = ceil(tiles / G): one contiguous range per workgroup (the windows in flight at once
+// lie n / G records apart, which measured the fixed-256 pack 10 % slower than the tile loop,
+// profiles/r04_ab_vt.log; smaller chunks did not recover it, so vt_pays chooses per launch).  A
+// virtual tile the fast path cannot take (a record longer than a window, gather mode, a
+// PUBLISH_TOPIC length wrap) is written whole, window by window.
 template <class LY, bool kPacked>
 __device__ __forceinline__ TileIn vt_load(const EncArgs& a, uint64_t r0, int lane) {
     SBE_TILE_SHAPE(LY);
@@ -2030,7 +1959,7 @@ __device__ uint64_t g_vt_guard[16];
 
 template <class LY, bool kPacked, int kLen>
 __device__ __forceinline__ void enc_pack_run_vt(const EncArgs& a, uint64_t first, uint64_t G, PackLds<LY, kPacked>& L,
-                                                uint64_t chunk_tiles = SBE_VT_CHUNK, bool spread = false) {
+                                                bool spread = false) {
     SBE_TILE_SHAPE(LY);
     lds_u8* const wout = (lds_u8*)L.wout;
     lds_u8* const win_in = (lds_u8*)L.win + kInSlack;
@@ -2039,7 +1968,7 @@ __device__ __forceinline__ void enc_pack_run_vt(const EncArgs& a, uint64_t first
     uint64_t* const sbase = L.sbase;
     const int lane = threadIdx.x;
     const uint64_t ntiles = (a.n + kRpt - 1) / kRpt;
-    const uint64_t CT = chunk_tiles > 0 ? chunk_tiles : (ntiles + G - 1) / G;
+    const uint64_t CT = (ntiles + G - 1) / G;
     const uint64_t nch = (ntiles + CT - 1) / CT;
     uint64_t c = first;
     if (c >= nch) return;
@@ -2117,7 +2046,7 @@ __device__ __forceinline__ void enc_pack_run_vt(const EncArgs& a, uint64_t first
 #endif
     rn += advance(S, W, fast);
     if (kPacked) {
-        stage_issue<LY::kNtIn>(W.swb, W.nb, lane, I);
+        stage_issue(W.swb, W.nb, lane, I);
         stage_write(win_in, W.nb, lane, I);
     }
     // the next step: the rest of this chunk, or the workgroup's next chunk (its base from the
@@ -2160,7 +2089,7 @@ __device__ __forceinline__ void enc_pack_run_vt(const EncArgs& a, uint64_t first
                 x = vt_load<LY, kPacked>(a, rnn, lane);
             }
         }
-        if (have_next && kPacked) stage_issue<LY::kNtIn>(Wn.swb, Wn.nb, lane, I);
+        if (have_next && kPacked) stage_issue(Wn.swb, Wn.nb, lane, I);
         ph.lap(0);
         if (fast) {
             if (!compose_records<LY>(a, wout, win_in, rt, S, W.wrel, W.wlen, W.swb, W.nb, lane, W.ra, W.rb, ph, spread)) {
@@ -2224,16 +2153,13 @@ __device__ __forceinline__ void enc_pack_run_vt(const EncArgs& a, uint64_t first
     ph.put(lane);
 }
 
-// The batch pack kernel keeps the tile loop: per window, the virtual-tile loop re-prepares a tile
-// (lengths, scans, offsets) where the tile loop reuses the tile's state for its second window, and
-// that costs about what the full windows save (A/B in one process, pack µs tile → virtual tiles:
-// fixed-256 97 → 103-114, config 4 728 → 722-827, session 135 → 134-151, OrderRequestLite 145 →
-// 160, CommitOffsetLite 41 → 40-44 over chunk sizes 1-8 and contiguous ranges;
-// profiles/r04_ab_vt_chunks.log).  The serve kernel uses the virtual-tile loop (running offsets,
-// no tile sums).  SBE_PACK_VT=1 selects it for the batch kernel (A/B).
-#ifndef SBE_PACK_VT  // A/B builds: 1 = always the virtual-tile loop, 2 = never; 0 = chosen per launch
-#define SBE_PACK_VT 0
-#endif
+// The batch pack kernel chooses its loop per launch: per window, the virtual-tile loop re-prepares
+// a tile (lengths, scans, offsets) where the tile loop reuses the tile's state for its second
+// window, and that costs about what the full windows save (A/B in one process, pack µs tile →
+// virtual tiles: fixed-256 97 → 103-114, config 4 728 → 722-827, session 135 → 134-151,
+// OrderRequestLite 145 → 160, CommitOffsetLite 41 → 40-44 over chunk sizes 1-8 and contiguous
+// ranges; profiles/r04_ab_vt_chunks.log).  The serve kernel uses the virtual-tile loop (running
+// offsets, no tile sums).
 // Which loop pays is a matter of the windows a tile takes: a tile whose output ends in a part-full
 // window pays that window's fixed cost (staging issue, store rows, fix-up passes) for little, and
 // the virtual-tile loop (one contiguous record range per workgroup), whose windows are all full,
@@ -2259,8 +2185,8 @@ __device__ __forceinline__ bool vt_pays(const EncArgs& a) {
 template <class LY, bool kPacked, int kLen>
 __global__ __launch_bounds__(kWave, SBE_PACK_MIN_WAVES) void sbe_enc_pack(EncArgs a) {
     __shared__ PackLds<LY, kPacked> lds;
-    if (SBE_PACK_VT == 1 || (SBE_PACK_VT == 0 && kPacked && vt_pays<LY>(a)))
-        enc_pack_run_vt<LY, kPacked, kLen>(a, blockIdx.x, gridDim.x, lds, SBE_VT_CHUNK);
+    if (kPacked && vt_pays<LY>(a))
+        enc_pack_run_vt<LY, kPacked, kLen>(a, blockIdx.x, gridDim.x, lds);
     else
         enc_pack_run<LY, kPacked, kLen>(a, blockIdx.x, gridDim.x, lds);
 }
@@ -2651,9 +2577,6 @@ __device__ __forceinline__ uint64_t printable_mask64<LdsRec>(const LdsRec& R, ui
     return nbytes >= 64 ? m : m & ((1ull << nbytes) - 1);
 }
 
-#ifndef SBE_ACK_FAST
-#define SBE_ACK_FAST 1
-#endif
 // decode_acknowledgment_with_sbe (src/sbe_encoder.cpp:833-954)
 template <typename R_t>
 __device__ void dec_ack_heuristic(const R_t& R, uint32_t b, uint32_t len, Desc& d) {
@@ -2670,7 +2593,6 @@ __device__ void dec_ack_heuristic(const R_t& R, uint32_t b, uint32_t len, Desc& 
     // fields.  One 64-byte printable mask checks that for fields ending by byte 79; anything else
     // takes the general run scan.
     uint32_t nruns = 0;
-#if SBE_ACK_FAST
     if (len >= 22) {
         const uint32_t L1 = R.u16(b + 16);
         const uint32_t p2 = 18 + L1;
@@ -2692,7 +2614,6 @@ __device__ void dec_ack_heuristic(const R_t& R, uint32_t b, uint32_t len, Desc& 
             }
         }
     }
-#endif
     // maximal runs of printable bytes over [16, len), 64 bytes per block as a bitmask; a run may
     // continue into the next block
     uint64_t run_start = 0, run_len = 0;
@@ -2933,9 +2854,6 @@ __device__ __noinline__ Desc dec_record_glb(const uint8_t* in, uint64_t rs, uint
 // policy, rotated inputs, fixed-256 55.4 / 57.2 us, config 3 58.5 / 59.6, session frames 63.4 /
 // 65.6, OrderRequestLite 66.5 / 71.0; one set re-read, fixed-256 56.3 / 58.4, config 4 410.9 / 430.9
 // (profiles/r06_ab_decntl_{rot,warm}.log)
-#ifndef SBE_DEC_NTL  // A/B builds: 0 = the decode's staging loads with the default cache policy
-#define SBE_DEC_NTL 1
-#endif
 template <uint32_t kW>
 __device__ __forceinline__ void dec_issue(const DecArgs& a, uint64_t wb, uint64_t we, int lane,
                                           uint4 (&I)[dec_regs<kW>()]) {
@@ -2944,8 +2862,7 @@ __device__ __forceinline__ void dec_issue(const DecArgs& a, uint64_t wb, uint64_
 #pragma unroll
     for (int k = 0; k < dec_regs<kW>(); ++k) {
         const uint32_t ch = lane + kWave * k;
-        I[k] = ch < nch ? (SBE_DEC_NTL ? gload128_nt(src + 16ull * ch) : gload128(src + 16ull * ch))
-                        : make_uint4(0, 0, 0, 0);
+        I[k] = ch < nch ? gload128_nt(src + 16ull * ch) : make_uint4(0, 0, 0, 0);
     }
 }
 
@@ -2959,11 +2876,7 @@ __device__ __forceinline__ uint32_t dec_commit(uint32_t* win, uint64_t wb, uint6
         if (ch < nch) lds_write_chunk(win, ch, I[k]);
     }
     uint32_t sm = 0;
-#ifdef SBE_ABL_NOCLASS  // ablation builds only (wrong flags on payloads with a key or a backslash)
-    if (false) {
-#else
     if (kMode == SBE_DEC_PARSE_MESSAGE && wide) {
-#endif
         // rows of chunks past the window are skipped (a tile's later window is often part full);
         // zero chunks of the last row are never suspect
         const uint32_t nrow = (nch + kWave - 1) / kWave;
@@ -3013,12 +2926,8 @@ __device__ __forceinline__ void dec_window(const uint32_t* win, uint64_t wb, uin
     if (kMode == SBE_DEC_PARSE_MESSAGE) {
         const bool pend = here && (d.flags & kFlSeqPending);
         if (!wide) {
-#ifdef SBE_TIMING_NOSEQ  // timing builds only (scripts/serve_probe.cpp): the per-lane scan skipped
-            if (pend) d.flags &= ~kFlSeqPending;
-#else
             if (pend)
                 d.flags = (d.flags & ~kFlSeqPending) | has_seq_key_lane(LdsRec{win, (uint32_t)(rs - wb)}, d.off[3], d.len[3]);
-#endif
         } else if (__ballot(pend)) {
             uint32_t hit = 0;
             if (__ballot(sm != 0)) {  // some staged chunk holds a key slice or a backslash
@@ -3212,191 +3121,6 @@ __global__ __launch_bounds__(kWave, kWin == kWinWide && kWinWide > 16384 ? 2 : (
     dec_tile<kMode, kWin>(a, blockIdx.x, win);
 }
 
-// Decode of mixed batches with waves specialised by record kind (verdict r5 item 3).  In a tile of
-// config 3's mix (69 % TopicMessages, 30 % Acks) a wave runs both parse paths one after the other:
-// the TopicMessage lanes' payload scan with the Ack lanes idle, then the Ack lanes' printable-run
-// scan with the TopicMessage lanes idle.  A workgroup of kG waves stages the kG tiles' bytes into
-// one shared window, counts the TopicMessages and the Acks, and deals the records to the waves by
-// kind (TopicMessages first, in record order, then Acks): at most one wave of the group holds
-// both kinds.  Each lane parses its record from the shared window, and the descriptors go back to
-// record order through LDS before the stores, so each wave stores contiguous rows.  A record that
-// does not lie in the window (the group's bytes past kGW, or rec_off not increasing) is parsed
-// from HBM by its lane (dec_record_glb), as the one-wave kernel does with a record no window can
-// hold.  (A fallback to the one-wave path inside this kernel gave the parse functions a second
-// call site, so the compiler outlined them and passed each descriptor through scratch: 30 scratch
-// stores a wave, twice the decode time.)
-// The workgroups are persistent (occupancy x CUs) and take groups g, g + G, ...; the next group's
-// bytes are loaded into registers while the current one is parsed, and the offsets of the one
-// after it a step earlier still, so a group's two dependent HBM round trips (offsets, then bytes)
-// hide behind the previous group's work.  Every load of the loop is issued unconditionally (at a
-// clamped group index on the last step), so the compiler's waits count them exactly.
-struct GroupOffs {
-    uint64_t g0, wb, we;  // first record; staged window [wb, we) (uniform)
-    uint64_t rs, rl;      // this thread's record
-    bool valid;
-};
-template <uint32_t kT, uint32_t kGW>
-__device__ __forceinline__ GroupOffs group_offs(const DecArgs& a, uint64_t g, uint32_t tid) {
-    GroupOffs o;
-    o.g0 = g * kT;
-    const uint64_t r = o.g0 + tid;
-    o.valid = r < a.n;
-    const uint64_t last = o.g0 + kT < a.n ? o.g0 + kT : a.n;
-    const uint64_t T0 = uniform64(a.rec_off[o.g0]);
-    const uint64_t end = (uniform64(a.rec_off[last]) + 15) & ~15ull;
-    o.wb = T0 & ~15ull;
-    o.we = end <= o.wb ? o.wb : (end - o.wb <= kGW ? end : o.wb + kGW);
-    const uint64_t rc = o.valid ? r : a.n - 1;
-    o.rs = a.rec_off[rc];
-    o.rl = a.rec_off[rc + 1] - o.rs;
-    return o;
-}
-template <uint32_t kT, uint32_t kPerThr>
-__device__ __forceinline__ void group_issue(const DecArgs& a, const GroupOffs& o, uint32_t tid, uint4 (&I)[kPerThr]) {
-    const uint32_t nch = (uint32_t)((o.we - o.wb) >> 4);
-    const uintptr_t src = reinterpret_cast<uintptr_t>(a.in) + o.wb;
-#pragma unroll
-    for (uint32_t k = 0; k < kPerThr; ++k) {
-        const uint32_t ch = tid + kT * k;
-        I[k] = ch < nch ? gload128_nt(src + 16ull * ch) : make_uint4(0, 0, 0, 0);
-    }
-}
-
-template <uint32_t kMode, uint32_t kG, uint32_t kGW>
-__device__ __forceinline__ void dec_group(const DecArgs& a, uint32_t* win) {
-    constexpr uint32_t kT = kG * kWave;  // records of the group
-    constexpr uint32_t kPerThr = kGW / 16 / kT;  // staged chunks per thread
-    static_assert(kGW % (16 * kT) == 0, "group window shape");
-    __shared__ uint32_t rsA[kT], rlA[kT];
-    __shared__ uint16_t slot_rec[kT];
-    __shared__ uint32_t kcount[2 * kG];
-    const uint32_t tid = threadIdx.x, w = tid / kWave, lane = tid & (kWave - 1);
-    const uint64_t ngroups = (a.n + kT - 1) / kT, G = gridDim.x;
-    uint64_t g = blockIdx.x;
-    if (g >= ngroups) return;
-    auto clampg = [&](uint64_t x) { return x < ngroups ? x : ngroups - 1; };
-    GroupOffs o = group_offs<kT, kGW>(a, g, tid);
-    uint4 I[kPerThr];
-    group_issue<kT, kPerThr>(a, o, tid, I);
-    GroupOffs on = group_offs<kT, kGW>(a, clampg(g + G), tid);
-    for (;;) {
-        const bool has_next = g + G < ngroups;  // uniform
-        const uint64_t r = o.g0 + tid;
-        const bool inw = o.valid && o.rs >= o.wb && o.rs + o.rl <= o.we;  // parsed from the window
-        {
-            const uint32_t nch = (uint32_t)((o.we - o.wb) >> 4);
-#pragma unroll
-            for (uint32_t k = 0; k < kPerThr; ++k) {
-                const uint32_t ch = tid + kT * k;
-                if (ch < nch) lds_write_chunk(win, ch, I[k]);
-            }
-        }
-        rsA[tid] = inw ? (uint32_t)(o.rs - o.wb) : ~0u;
-        rlA[tid] = (uint32_t)(o.rl < 0xffffffffull ? o.rl : 0xffffffffull);
-        __syncthreads();
-        // the next group's bytes and the offsets of the one after it, in flight from here on
-        group_issue<kT, kPerThr>(a, on, tid, I);
-        const GroupOffs onn = group_offs<kT, kGW>(a, clampg(g + 2 * G), tid);
-        // kind of the record: an Ack (template 2, schema 1: the printable-run path) or anything else
-        uint32_t ack = 0;
-        if (inw && o.rl >= 8) {
-            const LdsRec R{win, (uint32_t)(o.rs - o.wb)};
-            const uint32_t h0 = R.u32(0), h1 = R.u32(4);
-            ack = (h0 >> 16) == 2u && (h1 & 0xffffu) == 1u;
-        }
-        const uint64_t below = (1ull << lane) - 1ull;
-        const uint64_t bt = __ballot(o.valid && !ack), ba = __ballot(o.valid && ack);
-        if (lane == 0) {
-            kcount[w] = (uint32_t)__builtin_popcountll(bt);
-            kcount[kG + w] = (uint32_t)__builtin_popcountll(ba);
-        }
-        __syncthreads();
-        uint32_t ntm = 0, pre_t = 0, pre_a = 0, nval = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kG; ++k) {
-            ntm += kcount[k];
-            nval += kcount[k] + kcount[kG + k];
-            pre_t += k < w ? kcount[k] : 0u;
-            pre_a += k < w ? kcount[kG + k] : 0u;
-        }
-        // invalid threads (the batch's last group) keep their own index, past the valid ones
-        const uint32_t slot = !o.valid ? tid
-                            : ack      ? ntm + pre_a + (uint32_t)__builtin_popcountll(ba & below)
-                                       : pre_t + (uint32_t)__builtin_popcountll(bt & below);
-        slot_rec[slot] = (uint16_t)tid;
-        __syncthreads();
-        // this lane's record: the tid-th of the dealt order
-        const uint32_t j = slot_rec[tid];
-        const bool jv = tid < nval;
-        Desc d;
-        d.clear();
-        const uint32_t jb = rsA[j], jl = rlA[j];
-        if (jv) {
-            if (jb != ~0u) {
-                dec_record<kMode>(LdsRec{win, jb}, jl, d);
-                if (kMode == SBE_DEC_PARSE_MESSAGE && (d.flags & kFlSeqPending))
-                    d.flags = (d.flags & ~kFlSeqPending) | has_seq_key_lane(LdsRec{win, jb}, d.off[3], d.len[3]);
-            } else {  // not in the window: from HBM
-                const uint64_t rj = o.g0 + j, sj = a.rec_off[rj], lj = a.rec_off[rj + 1] - sj;
-                if (lj > 0xffffffffull) dec_oversize<kMode>(d);
-                else d = dec_record_glb<kMode>(a.in, sj, (uint32_t)lj);
-            }
-        }
-        // the descriptors back in record order through LDS (the window is free once every lane
-        // has parsed), so each wave's stores cover contiguous rows as in the one-wave kernel
-        constexpr uint32_t kDs = 17;  // dwords per staged descriptor (odd: no bank conflicts)
-        static_assert(kDs * kT * 4 <= kGW, "descriptor staging fits the window");
-        __syncthreads();
-        if (jv) {
-            uint32_t* q = win + kDs * j;
-            q[0] = d.status | (d.flags << 8);
-            q[1] = (uint32_t)d.hdr[0] | ((uint32_t)d.hdr[1] << 16);
-            q[2] = (uint32_t)d.hdr[2] | ((uint32_t)d.hdr[3] << 16);
-            q[3] = (uint32_t)d.ts;
-            q[4] = (uint32_t)(d.ts >> 32);
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                q[5 + k] = d.off[k];
-                q[10 + k] = d.len[k];
-            }
-        }
-        __syncthreads();
-        Desc e;
-        e.clear();
-        if (o.valid) {
-            const uint32_t* q = win + kDs * tid;
-            e.status = q[0] & 0xffu;
-            e.flags = q[0] >> 8;
-            e.hdr[0] = (uint16_t)q[1];
-            e.hdr[1] = (uint16_t)(q[1] >> 16);
-            e.hdr[2] = (uint16_t)q[2];
-            e.hdr[3] = (uint16_t)(q[2] >> 16);
-            e.ts = (uint64_t)q[3] | ((uint64_t)q[4] << 32);
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                e.off[k] = q[5 + k];
-                e.len[k] = q[10 + k];
-            }
-        }
-        dec_outputs<kMode, false>(a, r, o.valid, o.rs, e);
-        if (!has_next) break;
-        __syncthreads();  // every thread is past its descriptor read before the window is rewritten
-        g += G;
-        o = on;
-        on = onn;
-    }
-}
-
-#ifndef SBE_DEC_GROUP  // A/B builds: tiles per workgroup of the group decode kernel (0: the one-wave mid kernel)
-#define SBE_DEC_GROUP 0
-#endif
-constexpr uint32_t kDecG = SBE_DEC_GROUP > 0 ? SBE_DEC_GROUP : 1;
-template <uint32_t kMode>
-__global__ __launch_bounds__(kDecG * kWave, kDecG >= 3 ? 2 : 3) void sbe_decode_group_kernel(DecArgs a) {
-    __shared__ uint32_t win[kDecG * kWinMid / 4];
-    dec_group<kMode, kDecG, kDecG * kWinMid>(a, win);
-}
-
 thread_local char g_last_error[256] = "";
 
 int record_hip(hipError_t e) {
@@ -3437,35 +3161,6 @@ uint64_t pack_grid(const void* kernel, uint64_t tiles) {
     // G/128 + 1 <= 64
     if (g > (uint64_t)(kWave - 1) * kTilesPerSb) g = (uint64_t)(kWave - 1) * kTilesPerSb;
     return tiles < g ? tiles : g;
-}
-
-// Persistent grid of the group decode kernel (kDecG waves a workgroup): occupancy x CUs, at most
-// one workgroup per group.
-uint64_t group_grid(const void* kernel, uint64_t groups) {
-    static thread_local const void* ck[4] = {};
-    static thread_local int cdev[4] = {};
-    static thread_local uint64_t cg[4] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    uint64_t g = 0;
-    for (int i = 0; i < 4; ++i)
-        if (ck[i] == kernel && cdev[i] == dev) g = cg[i];
-    if (g == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kDecG * kWave, 0) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-        g = (uint64_t)per_cu * (uint64_t)cus;
-        for (int i = 0; i < 4; ++i)
-            if (ck[i] == nullptr) {
-                ck[i] = kernel;
-                cdev[i] = dev;
-                cg[i] = g;
-                break;
-            }
-    }
-    return groups < g ? groups : g;
 }
 
 // Optional launch profiling: every `g_prof_every`-th launch of the pack kernel and of the decode
@@ -3517,11 +3212,11 @@ void prof_commit(int which, hipEvent_t start) {
 // Aeron fragment reassembly (LocalFragmentReassembler::onFragment, src/cluster_client.cpp:39-82)
 //   1-3. the inclusive scan of one element per fragment (delivery-point count, last BEGIN, last
 //      END, singles, the accumulator as an affine map) in three launches (frag_reduce,
-//      frag_scan_blocks, frag_scan: the elements are classified on the fly, never stored)
-//   4. frag_messages: every delivery point (a BEGIN|END single, or an END) writes its message's
-//      offset and size from the accumulator map, and the first / last fragment of its group (the
-//      non-single fragments since the last BEGIN or END before it); the open group at the end of
-//      the batch is the carry
+//      frag_scan_blocks, frag_scan_msgs: the elements are classified on the fly, never stored)
+//   4. in frag_scan_msgs too: every delivery point (a BEGIN|END single, or an END) writes its
+//      message's offset and size from the accumulator map, and the first / last fragment of its
+//      group (the non-single fragments since the last BEGIN or END before it); the open group at
+//      the end of the batch is the carry
 //   5. frag_copy: one wave per 64 messages, runs of back-to-back messages copied as one block
 //      (fragment by fragment only when a single sits inside a group)
 // ------------------------------------------------------------------------------------------
@@ -3583,7 +3278,7 @@ __device__ __forceinline__ bool frag_single(uint8_t f) {
 // kernel + a generic device scan over the 24-B tuple, which ran at 0.6 TB/s): frag_reduce classifies each
 // 1024-fragment block on the fly and writes the block's aggregate; frag_scan_blocks turns the
 // aggregates into exclusive block prefixes (one workgroup, 1024 at a time with a carry);
-// frag_scan re-classifies and writes the inclusive scan.  Elements are never materialised.
+// frag_scan_msgs re-classifies and scans each block again.  Elements are never materialised.
 #ifndef SBE_FS_PER  // A/B builds: fragments per thread of the scan launches
 #define SBE_FS_PER 4
 #endif
@@ -3691,84 +3386,16 @@ __global__ __launch_bounds__(kFsbThreads) void frag_scan_blocks(FragScan* agg, u
         carry = FragScanOp{}(carry, tot);
     }
 }
-__global__ __launch_bounds__(kFsThreads) void frag_scan(FragArgs a, const FragScan* pre) {
-    __shared__ FragScan wt[kFsThreads / kWave];
-    const uint64_t b = blockIdx.x;
-    FragScan e[kFsPer], before;
-    (void)fs_block(a, b, e, wt, before);
-    const FragScan base = FragScanOp{}(pre[b], before);
-    const uint64_t i0 = b * kFsBlk + (uint64_t)threadIdx.x * kFsPer;
-#pragma unroll
-    for (int k = 0; k < kFsPer; ++k)
-        if (i0 + k < a.n) a.sc[i0 + k] = FragScanOp{}(base, e[k]);
-}
 
-// group of non-single fragments ending at i (inclusive): from the later of the last BEGIN at or
-// before i and the fragment after the last END before i
-// (its bytes come from the accumulator map: FragScan)
-__device__ __forceinline__ void frag_group(const FragArgs& a, uint64_t i, int64_t le_before, uint64_t& s, bool& gap) {
-    const FragScan& e = a.sc[i];
-    int64_t st = (int64_t)e.lb > le_before + 1 ? (int64_t)e.lb : le_before + 1;
-    if (st < 0) st = 0;
-    s = (uint64_t)st;
-    const uint32_t sg0 = s ? fs_sg(a.sc[s - 1]) : 0u;
-    gap = fs_sg(e) != sg0;
-}
-
-__global__ __launch_bounds__(256) void frag_messages(FragArgs a) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    const uint8_t f = a.flags[i];
-    const FragScan e = a.sc[i];
-    const uint64_t E0 = i ? a.sc[i - 1].E : 0ull;  // delivered bytes before fragment i
-    const bool single = frag_single(f);
-    const uint32_t dp = fs_dp(e);
-    if ((single || (f & SBE_FRAG_END)) && dp >= 1 && dp <= a.n) {
-        const uint64_t j = dp - 1;
-        a.msize[j] = e.E - E0;
-        a.msg_off[j] = E0;
-        if (single) {
-            a.mfirst[j] = i;
-            a.mlast[j] = i;
-        } else {
-            uint64_t s;
-            bool gap;
-            frag_group(a, i, i ? a.sc[i - 1].le : -1, s, gap);
-            a.mfirst[j] = s;
-            a.mlast[j] = i | (gap ? (1ull << 63) : 0ull);
-        }
-    }
-    if (i == a.n - 1) {  // the open accumulator after the last fragment: the carry
-        const uint64_t m = dp <= a.n ? dp : a.n;
-        uint64_t s;
-        bool gap;
-        frag_group(a, i, e.le, s, gap);
-        const uint64_t bytes = e.B;  // pending bytes after the last fragment
-        const bool open = (int64_t)s <= (int64_t)i && bytes > 0;
-        a.msize[m] = open ? bytes : 0u;
-        a.msg_off[m] = e.E;
-        a.mfirst[m] = s;
-        a.mlast[m] = i | (gap ? (1ull << 63) : 0ull);
-        a.counts[0] = m;
-        a.counts[1] = open ? bytes : 0u;
-    }
-}
-
-// frag_scan and frag_messages in one launch (the default): the block's inclusive scan stays in
-// registers (and the singles counts in LDS) instead of a 32-B element per fragment written to HBM
-// and read back.  A group that starts before the block finds the singles before its start from
-// the block's exclusive prefix minus the singles between its start and the block (few fragments:
-// groups are short).
-#ifndef SBE_FRAG_FUSED  // A/B builds: 0 = frag_scan + frag_messages
-#define SBE_FRAG_FUSED 1
-#endif
+// frag_scan_msgs: the third scan launch and the message table in one.  The block's inclusive scan
+// stays in registers (and the singles counts in LDS) instead of a 32-B element per fragment written
+// to HBM and read back by a kernel of its own.  A group that starts before the block finds the
+// singles before its start from the block's exclusive prefix minus the singles between its start
+// and the block (few fragments: groups are short).
 // The block's messages are the consecutive indices [dp before the block, dp after it): their four
 // table entries go through LDS, one array at a time, and leave as contiguous 8-B stores per lane
 // (stored straight from each fragment's lane, a wave's 64 stores land 32 B apart and the table
 // cost 56.6 MB of HBM writes for 32 MB of entries, profiles/r05_reasm2_summary.txt).
-#ifndef SBE_FRAG_STAGE
-#define SBE_FRAG_STAGE 1
-#endif
 // Singles among fragments [0, x] for an x in an earlier block than b (rare: the start of a group
 // that crosses into block b; out of line, so its registers stay out of frag_scan_msgs): from the
 // nearer block boundary, counting the singles between it and x from 16-byte aligned flag loads (at
@@ -3805,11 +3432,9 @@ __device__ __noinline__ uint32_t frag_singles_before(const FragArgs& a, const Fr
 __global__ __launch_bounds__(kFsThreads) void frag_scan_msgs(FragArgs a, const FragScan* pre) {
     __shared__ FragScan wt[kFsThreads / kWave];
     __shared__ uint32_t sgl[kFsBlk];  // inclusive singles count at every fragment of the block
-#if SBE_FRAG_STAGE
     __shared__ uint64_t stg[kFsBlk];  // one table array of the block's messages
     uint64_t tv[kFsPer][4];
     uint32_t tj[kFsPer];              // message index - j0, or ~0u (no message at this fragment)
-#endif
     const uint64_t b = blockIdx.x;
     FragScan e[kFsPer], before;
     const FragScan tot = fs_block(a, b, e, wt, before);
@@ -3827,18 +3452,18 @@ __global__ __launch_bounds__(kFsThreads) void frag_scan_msgs(FragArgs a, const F
     auto sg_at = [&](uint64_t x) -> uint32_t {  // singles among fragments [0, x]
         return x >= blk0 ? sgl[x - blk0] : frag_singles_before(a, pre, x, b);
     };
-    auto group = [&](const FragScan& x, int64_t le_before, uint64_t& s0, bool& gap) {  // frag_group
+    // group of non-single fragments ending at x's fragment (inclusive): from the later of the last
+    // BEGIN at or before it and the fragment after the last END before it
+    auto group = [&](const FragScan& x, int64_t le_before, uint64_t& s0, bool& gap) {
         int64_t st = (int64_t)x.lb > le_before + 1 ? (int64_t)x.lb : le_before + 1;
         if (st < 0) st = 0;
         s0 = (uint64_t)st;
         const uint32_t sg0 = s0 ? sg_at(s0 - 1) : 0u;
         gap = fs_sg(x) != sg0;
     };
-#if SBE_FRAG_STAGE
     const uint32_t j0 = fs_dp(P), nj = fs_dp(tot);  // the block's messages: [j0, j0 + nj)
 #pragma unroll
     for (int k = 0; k < kFsPer; ++k) tj[k] = ~0u;
-#endif
 #pragma unroll
     for (int k = 0; k < kFsPer; ++k) {
         const uint64_t i = i0 + k;
@@ -3861,18 +3486,11 @@ __global__ __launch_bounds__(kFsThreads) void frag_scan_msgs(FragArgs a, const F
             }
             if (a.big && !(last >> 63) && x.E - E0 >= kFcBig)  // rare: a few per batch at most
                 a.big[1 + atomicAdd(reinterpret_cast<unsigned long long*>(a.big), 1ull)] = j;
-#if SBE_FRAG_STAGE
             tj[k] = (uint32_t)(j - j0);
             tv[k][0] = x.E - E0;
             tv[k][1] = E0;
             tv[k][2] = first;
             tv[k][3] = last;
-#else
-            a.msize[j] = x.E - E0;
-            a.msg_off[j] = E0;
-            a.mfirst[j] = first;
-            a.mlast[j] = last;
-#endif
         }
         if (i == a.n - 1) {  // the open accumulator after the last fragment: the carry
             const uint64_t m = dp <= a.n ? dp : a.n;
@@ -3891,7 +3509,6 @@ __global__ __launch_bounds__(kFsThreads) void frag_scan_msgs(FragArgs a, const F
                 a.big[1 + atomicAdd(reinterpret_cast<unsigned long long*>(a.big), 1ull)] = m;
         }
     }
-#if SBE_FRAG_STAGE
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
 #pragma unroll
@@ -3902,52 +3519,25 @@ __global__ __launch_bounds__(kFsThreads) void frag_scan_msgs(FragArgs a, const F
         for (uint32_t t = tid; t < nj; t += kFsThreads) dst[t] = stg[t];
         __syncthreads();
     }
-#endif
 }
 
-// the 16 bytes at src + 16c + sh from the aligned blocks b0 (at 16c) and b1 (the next one)
-__device__ __forceinline__ uint4 join16(uint4 b0, uint4 b1, uint32_t sh) {
-    const uint32_t w[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-    const uint32_t ds = sh >> 2, bs = sh & 3u;
-    uint32_t v[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t)  // v[t] = w[t + ds] (selects keep w in registers)
-        v[t] = ds == 0 ? w[t] : ds == 1 ? w[t + 1] : ds == 2 ? w[t + 2] : w[t + 3 < 8 ? t + 3 : 7];
-    return make_uint4(__builtin_amdgcn_alignbyte(v[1], v[0], bs), __builtin_amdgcn_alignbyte(v[2], v[1], bs),
-                      __builtin_amdgcn_alignbyte(v[3], v[2], bs), __builtin_amdgcn_alignbyte(v[4], v[3], bs));
-}
-
-// wave copy of src[0, len) to dst with 16-byte stores once dst is aligned; each output chunk
-// joins the two aligned 16-byte source blocks it spans (never past the source's last block);
-// four chunks per lane per step, all eight loads issued before the first join
+// wave copy of src[0, len) to dst with 16-byte nontemporal stores once dst is aligned; four chunks
+// per lane per step, all their loads issued before the first store
 #ifndef SBE_FC_U  // A/B builds: chunks per lane per copy step
 #define SBE_FC_U 4
 #endif
 constexpr int kFcU = SBE_FC_U;
 // One unaligned 16-byte load per output chunk (a single global_load_dwordx4 at any byte address)
 // instead of the two aligned blocks it spans joined with v_alignbyte: reassembly row 188.4 ->
-// 185.3 us (profiles/r05_ab_fragcopy.log); SBE_FC_UA=0 builds the joined form.
-#ifndef SBE_FC_UA
-#define SBE_FC_UA 1
-#endif
-#ifndef SBE_FC_NT
-#define SBE_FC_NT 1
-#endif
+// 185.3 us (profiles/r05_ab_fragcopy.log).
 typedef u32x4 u32x4_a1 __attribute__((aligned(1)));
 typedef __attribute__((address_space(1))) const u32x4_a1 g_u32x4_a1;
 // The copy's source loads are nontemporal (each fragment is read once): on rotated inputs the row
 // read 157.0 / 157.0 / 156.9 -> 154.9 / 155.8 / 154.2 us over three alternations
 // (profiles/r06_ab_fc_rot.log; round 5, re-reading one batch every step, had them slower, 149.7 ->
 // 163.4 us); 2 / 8 chunks a lane a step 160.4-161.1 / 157.7-159.4 us.
-#ifndef SBE_FC_NTL  // A/B builds: 0 = default-policy source loads
-#define SBE_FC_NTL 1
-#endif
 __device__ __forceinline__ uint4 gload128_ua(uintptr_t addr) {  // any byte address (one global_load_dwordx4)
-#if SBE_FC_NTL
     const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<g_u32x4_a1*>(addr));
-#else
-    const u32x4 v = *reinterpret_cast<g_u32x4_a1*>(addr);
-#endif
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void wave_copy16(uint8_t* dst, const uint8_t* src, uint64_t len, int lane) {
@@ -3958,7 +3548,6 @@ __device__ __forceinline__ void wave_copy16(uint8_t* dst, const uint8_t* src, ui
     const uint64_t nc = (len - head) >> 4;
     const uintptr_t p0 = reinterpret_cast<uintptr_t>(src) + head;
     uint4* d16 = reinterpret_cast<uint4*>(dst + head);
-#if SBE_FC_UA
     // the chunk's 16 source bytes in one load at their own (unaligned) address: no join, half the
     // loads (every byte read lies inside the source)
     for (uint64_t c0 = 0; c0 < nc; c0 += kFcU * kWave) {
@@ -3971,36 +3560,13 @@ __device__ __forceinline__ void wave_copy16(uint8_t* dst, const uint8_t* src, ui
 #pragma unroll
         for (int u = 0; u < kFcU; ++u) {
             const uint64_t c = c0 + (uint64_t)lane + (uint64_t)kWave * u;
-#if SBE_FC_NT  // nontemporal (streamed) stores, as the pack and decode kernels' outputs
-            if (c < nc) {
+            if (c < nc) {  // nontemporal (streamed) stores, as the pack and decode kernels' outputs
                 u32x4 v;
                 v.x = x[u].x, v.y = x[u].y, v.z = x[u].z, v.w = x[u].w;
                 __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(d16 + c));
             }
-#else
-            if (c < nc) d16[c] = x[u];
-#endif
         }
     }
-#else
-    const uint32_t sh = (uint32_t)(p0 & 15u);
-    const uintptr_t q0 = p0 & ~(uintptr_t)15;
-    for (uint64_t c0 = 0; c0 < nc; c0 += kFcU * kWave) {
-        uint4 x[kFcU], y[kFcU];
-#pragma unroll
-        for (int u = 0; u < kFcU; ++u) {
-            const uint64_t c = c0 + (uint64_t)lane + (uint64_t)kWave * u;
-            const uintptr_t q = q0 + 16 * (c < nc ? c : nc - 1);
-            x[u] = gload128(q);
-            y[u] = gload128(q + (sh ? 16 : 0));
-        }
-#pragma unroll
-        for (int u = 0; u < kFcU; ++u) {
-            const uint64_t c = c0 + (uint64_t)lane + (uint64_t)kWave * u;
-            if (c < nc) d16[c] = sh ? join16(x[u], y[u], sh) : x[u];
-        }
-    }
-#endif
     const uint64_t t0 = head + 16 * nc;
     if ((uint64_t)lane < len - t0) dst[t0 + lane] = src[t0 + lane];
 }
@@ -4010,38 +3576,15 @@ __device__ __forceinline__ void wave_copy16(uint8_t* dst, const uint8_t* src, ui
 // complete groups: the common case) form runs, each copied as one block; a message with a single
 // inside its group is copied fragment by fragment.
 constexpr int kFragGroup = 64;
-#ifndef SBE_FC_PF  // A/B builds: prefetch the next group's message metadata during the copy
-#define SBE_FC_PF 0
-#endif
 __global__ __launch_bounds__(256) void frag_copy(FragArgs a) {
     const int lane = threadIdx.x & (kWave - 1);
     const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / kWave);
     const uint64_t m = a.counts[0];
     const uint64_t base0 = ((uint64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave) * kFragGroup;
     const uint64_t step = waves * kFragGroup;
-#if SBE_FC_PF
-    // the next group's metadata is loaded while this group is copied (clamped index, loaded
-    // unconditionally: no wait on it before the copy)
-    auto meta = [&](uint64_t b, uint64_t& len_, uint64_t& first_, uint64_t& mlast_, uint64_t& dst_) {
-        uint64_t jj = b + (uint64_t)lane;
-        jj = jj <= m ? jj : m;
-        len_ = a.msize[jj];
-        first_ = a.mfirst[jj];
-        mlast_ = a.mlast[jj];
-        dst_ = a.msg_off[jj];
-    };
-    uint64_t nlen, nfirst, nmlast, ndst;
-    meta(base0, nlen, nfirst, nmlast, ndst);
-#endif
     for (uint64_t base = base0; base <= m; base += step) {
         const uint64_t j = base + (uint64_t)lane;
         const bool valid = lane < kFragGroup && j <= m;
-#if SBE_FC_PF
-        uint64_t len = nlen, first = nfirst, mlast = nmlast, dst = ndst;
-        uint64_t src = a.frag_off[first];
-        if (!valid) len = src = dst = mlast = first = 0;
-        meta(base + step, nlen, nfirst, nmlast, ndst);
-#else
         uint64_t len = 0, src = 0, dst = 0, mlast = 0, first = 0;
         if (valid) {
             len = a.msize[j];
@@ -4050,7 +3593,6 @@ __global__ __launch_bounds__(256) void frag_copy(FragArgs a) {
             dst = a.msg_off[j];
             src = a.frag_off[first];
         }
-#endif
         const bool gap = valid && (mlast >> 63);
         // a listed big message (frag_scan_msgs) is copied by all waves after the loop: it takes no
         // part in a run here, as a gapped message does not
@@ -4263,9 +3805,6 @@ __device__ __forceinline__ uint64_t mat_wave_max(uint64_t v) {
 // (from the view's start, or ending at its end) and its bytes stored one by one.
 // (nontemporal view loads: 0.165 -> 0.244 ms, profiles/r06_ab_matntl.log: a record's later chunks
 // re-read the lines its first loads brought in)
-#ifndef SBE_MAT_NTL  // A/B builds: 1 = the views' loads nontemporal
-#define SBE_MAT_NTL 0
-#endif
 __device__ __forceinline__ void mat_views_lds(mat_lds8* w, const uint8_t* rec, uint64_t rl, const uint64_t (&at)[6],
                                               const uint32_t (&L)[5], const uint32_t (&O)[5], int k_end) {
     uint32_t cc[6];  // first chunk of each view
@@ -4312,8 +3851,7 @@ __device__ __forceinline__ void mat_views_lds(mat_lds8* w, const uint8_t* rec, u
             }
             dof[b] = d;
             if (q < nq && bm[b] <= 16)
-                v[b] = SBE_MAT_NTL ? __builtin_nontemporal_load(reinterpret_cast<const u32x4_ua*>(rec + s))
-                                   : *reinterpret_cast<const u32x4_ua*>(rec + s);
+                v[b] = *reinterpret_cast<const u32x4_ua*>(rec + s);
         }
 #pragma unroll
         for (int b = 0; b < kMatBatch; ++b) {
@@ -4328,8 +3866,8 @@ __device__ __forceinline__ void mat_views_lds(mat_lds8* w, const uint8_t* rec, u
         }
     }
 }
-// A tile's descriptors, loaded one tile ahead (unconditional loads at clamped indices, so the
-// compiler's waits count them exactly and the next tile's loads stay in flight during this copy)
+// A tile's descriptors (unconditional loads at clamped indices, so the compiler's waits count
+// them exactly)
 struct MatDesc {
     uint32_t L[5], O[5];
     uint64_t r0, r1, pre, bs;
@@ -4418,27 +3956,15 @@ __device__ __forceinline__ void mat_tile(const MatArgs& a, uint64_t t, const Mat
         start = mat_wave_min(done ? ~0ull : o);
     }
 }
-// SBE_MAT_PERSIST (A/B builds): 1 = a persistent grid (occupancy x CUs) whose waves loop over the
-// tiles with the next tile's descriptors in flight: 0.201 ms against 0.164 for one workgroup per
-// tile (profiles/r06_ab_mat6.log; a tile's loads then wait behind the previous tile's stores)
-#ifndef SBE_MAT_PERSIST
-#define SBE_MAT_PERSIST 0
-#endif
+// One workgroup per tile (a persistent grid, occupancy x CUs, whose waves loop over the tiles with
+// the next tile's descriptors in flight: 0.201 ms against 0.164, profiles/r06_ab_mat6.log; a
+// tile's loads then wait behind the previous tile's stores)
 __global__ __launch_bounds__(kWave, SBE_MAT_MINW) void mat_copy(MatArgs a, uint64_t nt) {
     __shared__ __attribute__((aligned(16))) uint8_t win[kMatWin];
     const int lane = threadIdx.x;
     MatDesc d;
     mat_desc_load(a, blockIdx.x, nt, lane, d);
-    if (!SBE_MAT_PERSIST) {
-        mat_tile(a, blockIdx.x, d, lane, win);
-        return;
-    }
-    for (uint64_t t = blockIdx.x; t < nt; t += gridDim.x) {
-        MatDesc dn;
-        mat_desc_load(a, t + gridDim.x, nt, lane, dn);
-        mat_tile(a, t, d, lane, win);
-        d = dn;
-    }
+    mat_tile(a, blockIdx.x, d, lane, win);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4657,7 +4183,7 @@ __device__ __forceinline__ void serve_encode(const EncArgs& a, PackLds<LY, true>
         return;
     }
     // one chunk (the zero prefix of tile 0 is the only base), chunks spread over the wave
-    enc_pack_run_vt<LY, true, kLen>(a, 0, 1, L, 0, true);
+    enc_pack_run_vt<LY, true, kLen>(a, 0, 1, L, true);
 }
 
 #ifdef SBE_SERVE_PROF
@@ -4688,7 +4214,13 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
         const uint64_t h = __hip_atomic_load(&dev->hdr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return uniform64(h);
     };
-    uint32_t last = leader ? __builtin_amdgcn_readfirstlane(sys_acquire(&slot->done_seq)) : (uint32_t)dev_hdr();
+    // The last request answered before this workgroup started.  A follower takes it from the host
+    // slot as the leader does, not from dev->hdr: one that starts after the leader has republished
+    // the launch's first request would take that request for an old one, never arrive, and leave
+    // its tiles unwritten.  done_seq cannot pass a request this follower takes part in before it
+    // has arrived; a header at or before it is an answered request's (a one-workgroup request
+    // leaves the header of an earlier wide one in place).
+    uint32_t last = __builtin_amdgcn_readfirstlane(sys_acquire(&slot->done_seq));
     uint64_t t_idle = __builtin_amdgcn_s_memrealtime();
     for (;;) {
         uint32_t seq;
@@ -4707,7 +4239,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
         } else {
             h = dev_hdr();
             seq = (uint32_t)h;
-            if (seq == last) {
+            if ((int32_t)(seq - last) <= 0) {  // nothing newer than the last request seen
                 if (__builtin_amdgcn_readfirstlane(
                         __hip_atomic_load(&dev->quit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == epoch)
                     break;
@@ -4853,8 +4385,10 @@ constexpr size_t kServeWsBytes = kServeScratchOff + kServeInline;
 
 int serve_launch(sbe_server* s) {
     __atomic_store_n(&s->h->alive, 1u, __ATOMIC_RELEASE);
-    // the exit count of the previous launch back to 0 (stream order: before the kernel starts)
-    if (const int rc = record_hip(hipMemsetAsync(&s->dev->exited, 0, sizeof(uint32_t), s->stream))) return rc;
+    // the exit count of the previous launch back to 0, and the arrival count with it, which a request
+    // the previous grid left unanswered may have moved (stream order: before the kernel starts)
+    static_assert(offsetof(ServeDev, exited) == offsetof(ServeDev, arrive) + sizeof(uint32_t), "one memset");
+    if (const int rc = record_hip(hipMemsetAsync(&s->dev->arrive, 0, 2 * sizeof(uint32_t), s->stream))) return rc;
     ++s->launches;
     hipLaunchKernelGGL(sbe_serve_kernel, dim3(s->nwg), dim3(kWave), 0, s->stream, s->d, s->idle_ticks,
                        reinterpret_cast<uint8_t*>(s->ws) + kServeScratchOff, s->dev, (uint32_t)s->launches);
@@ -5122,11 +4656,6 @@ int sbe_decode_batch_sized(const uint8_t* in, const uint64_t* rec_off, uint64_t 
             hipExtLaunchKernelGGL((sbe_decode_kernel<M, kWinLarge>), grid, block, 0, s, e0, e1, 0, a);     \
         else if (shape == 1)                                                                               \
             hipExtLaunchKernelGGL((sbe_decode_kernel<M, kWinWide>), grid, block, 0, s, e0, e1, 0, a);      \
-        else if (shape == 2 && SBE_DEC_GROUP > 0)                                                          \
-            hipExtLaunchKernelGGL((sbe_decode_group_kernel<M>),                                             \
-                                  dim3((uint32_t)group_grid((const void*)sbe_decode_group_kernel<M>,       \
-                                                            (n + kDecG * kTile - 1) / (kDecG * kTile))),    \
-                                  dim3(kDecG * kWave), 0, s, e0, e1, 0, a);                                \
         else if (shape == 2)                                                                               \
             hipExtLaunchKernelGGL((sbe_decode_kernel<M, kWinMid>), grid, block, 0, s, e0, e1, 0, a);       \
         else if (shape == 3)                                                                               \
@@ -5443,8 +4972,7 @@ int sbe_materialize_views(const uint8_t* in, const uint64_t* rec_off, uint64_t n
     MatArgs a{in, rec_off, n, dec->status, dec->view_off, dec->view_len, arena, arena_capacity, arena_off, bsum, bsum + nb};
     hipLaunchKernelGGL(mat_sums, dim3((uint32_t)nb), dim3(kMatBlk), 0, s, a);
     hipLaunchKernelGGL(mat_scan_blocks, dim3(1), dim3(kMatBlk), 0, s, a, nb);
-    const uint64_t g = SBE_MAT_PERSIST ? pack_grid(reinterpret_cast<const void*>(&mat_copy), nt) : nt;
-    hipLaunchKernelGGL(mat_copy, dim3((uint32_t)g), dim3(kWave), 0, s, a, nt);
+    hipLaunchKernelGGL(mat_copy, dim3((uint32_t)nt), dim3(kWave), 0, s, a, nt);
     return record_hip(hipGetLastError());
 }
 
@@ -5680,29 +5208,15 @@ int sbe_reassemble_fragments(const uint8_t* in, const uint64_t* frag_off, const 
     uint64_t* msize = ws.take<uint64_t>(n + 1);
     uint64_t* mfirst = ws.take<uint64_t>(n + 1);
     uint64_t* mlast = ws.take<uint64_t>(n + 1);
-    // the big-message list lives in sc[], which the fused scan does not use (n + 2 <= 4n words)
-#ifndef SBE_FRAG_BIG  // A/B builds: 0 = no big-message list (every message copied by its own wave)
-#define SBE_FRAG_BIG 1
-#endif
+    // the big-message list lives in sc[], which the scan does not use (n + 2 <= 4n words)
     FragArgs a{in, frag_off, flags, n, out, msg_off, counts, el, sc, msize, mfirst, mlast,
-               SBE_FRAG_FUSED && SBE_FRAG_BIG ? reinterpret_cast<uint64_t*>(sc) : nullptr};
-    const uint32_t blocks = (uint32_t)((n + 1 + 255) / 256);
+               reinterpret_cast<uint64_t*>(sc)};
     const uint64_t nb = (n + kFsBlk - 1) / kFsBlk;
     hipLaunchKernelGGL(frag_reduce, dim3((uint32_t)nb), dim3(kFsThreads), 0, s, a, el);
     hipLaunchKernelGGL(frag_scan_blocks, dim3(1), dim3(kFsbThreads), 0, s, el, nb, a.big);
-    hipError_t e = hipSuccess;
-    if (SBE_FRAG_FUSED) {
-        hipLaunchKernelGGL(frag_scan_msgs, dim3((uint32_t)nb), dim3(kFsThreads), 0, s, a, static_cast<const FragScan*>(el));
-        e = hipGetLastError();
-        if (e != hipSuccess) return record_hip(e);
-    } else {
-        hipLaunchKernelGGL(frag_scan, dim3((uint32_t)nb), dim3(kFsThreads), 0, s, a, static_cast<const FragScan*>(el));
-        e = hipGetLastError();
-        if (e != hipSuccess) return record_hip(e);
-        hipLaunchKernelGGL(frag_messages, dim3(blocks), dim3(256), 0, s, a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return record_hip(e);
-    }
+    hipLaunchKernelGGL(frag_scan_msgs, dim3((uint32_t)nb), dim3(kFsThreads), 0, s, a, static_cast<const FragScan*>(el));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return record_hip(e);
     const uint64_t cb = (n + 1 + 4 * kFragGroup - 1) / (4 * kFragGroup);  // four waves per block
 #ifndef SBE_FC_MAXB  // A/B builds: the copy's grid cap (blocks of four waves; they loop over the groups)
 #define SBE_FC_MAXB 4096

@@ -23,38 +23,18 @@ VARIANTS = {
                  ("    if (__ballot(i0 + 1 < n_mine)) {\n        group(", "    if (__ballot(i0 + 1 < n_mine && n_mine < 0)) {\n        group("),
                  ("    if (__ballot(i0 < n_mine)) group(", "    if (__ballot(i0 < n_mine && n_mine < 0)) group(")],
     "nocompose": [("    if (__ballot(!ok)) return false;\n", "    if (__ballot(!ok)) return false;\n    return true;\n")],
-    # decode tiles of 48 / 32 records (lanes past the tile idle) in 12 / 8 KiB windows: more
-    # workgroups per CU (LDS-bound at 16 KiB) against idle parse lanes
-    "t48": [("constexpr int kTile = 64; ", "constexpr int kTile = 48; "),
-            ("constexpr uint32_t kWin = 16384; ", "constexpr uint32_t kWin = 12288; "),
-            ("    const uint64_t r = t0 + (uint64_t)lane;\n    const bool valid = r < a.n;",
-             "    const uint64_t r = t0 + (uint64_t)lane;\n    const bool valid = lane < kTile && r < a.n;")],
-    "t32": [("constexpr int kTile = 64; ", "constexpr int kTile = 32; "),
-            ("constexpr uint32_t kWin = 16384; ", "constexpr uint32_t kWin = 8192; "),
-            ("    const uint64_t r = t0 + (uint64_t)lane;\n    const bool valid = r < a.n;",
-             "    const uint64_t r = t0 + (uint64_t)lane;\n    const bool valid = lane < kTile && r < a.n;")],
-    # the fast loop's input staging (loads + LDS writes)
-    "nostage": [("        if (have_next && kPacked) stage_issue(Wn.swb, Wn.nb, lane, I);\n", ""),
-                ("        if (kPacked) stage_write(win_in, Wn.nb, lane, I);  // after the compose above read win_in\n", "")],
-    # chunk-owner path (long records): skip chunk_pass / literal_pass
-    "nochunk": [("    chunk_pass(wout, inb, rt, bk, wlen, nb, kk, lg, lane);\n", "")],
+    # chunk-owner path (long records): skip literal_pass
     "nolitpass": [("    literal_pass<LY>(ea, wout, rt, S, wlen, lane);\n}", "}")],
-    "nofixw": [("    wsync();\n    zone_fixup<LY>(wout, inb, rt, wlen, nb, lane);\n    wsync();\n    literal_pass", "    wsync();\n    literal_pass")],
     "notables": [("    const bool outside = build_tables<LY>(rt, bk, sbase, S, wrel, wlen, swb, nb, ra, rb, lg, lane);\n",
                   "    const bool outside = false;\n")],
-    # the fast path's window store
     # Order JSON writer (substitutions in order_json.hpp, inlined into the variant): number
-    # formatting / string quoting / the window stores left out (measure and write agree on sizes)
+    # formatting / the window stores left out (measure and write agree on sizes)
     "oj_nonum": [("OJ", "    s = fmt_g17(s, q);\n", "    s.put('1');\n"), ("OJ", "    s = fmt_fixed6(s, q);\n", "    s.put('1');\n")],
-    "oj_noquote": [("OJ", "__device__ __noinline__ S quoted(S s, gu8* p, uint64_t len) {\n",
-                    "__device__ __noinline__ S quoted(S s, gu8* p, uint64_t len) {\n    if (len < ~0ull) { s.put('\"'); s.put('\"'); return s; }\n")],
     "oj_nostore": [("OJ", "        for (uint64_t c = lane; c < nch; c += kWWave) {", "        for (uint64_t c = nch + lane; c < nch; c += kWWave) {")],
     # decode: the Ack printable-run scan / the per-lane _sequence_number scan left out (config 3)
     "noack": [("    // maximal runs of printable bytes over [16, len)", "    if (len) return;\n    // maximal runs of printable bytes over [16, len)")],
     "noseqlane": [("__device__ uint32_t has_seq_key_lane(const LdsRec& R, uint32_t p, uint32_t n) {\n    if (n < 16) return 0u;",
                    "__device__ uint32_t has_seq_key_lane(const LdsRec& R, uint32_t p, uint32_t n) {\n    if (n < ~0u) return 0u;")],
-    "nostore": [("            store_window(a.out, a.sink, wout, S.T0 + W.A, S.T0 + (int64_t)W.wrel, "
-                 "S.T0 + (int64_t)(W.wrel + W.wlen),\n                         lane);\n", "")],
 }
 
 

@@ -406,3 +406,25 @@ def test_wide_alternating_and_relaunch(codec):
         assert launches >= 3
     finally:
         s.close()
+
+
+def test_wide_first_request_of_a_launch(codec):
+    """A wide request posted before its grid is launched (every request after a quiesce or an idle
+    exit): the leader may republish it before a follower has started, and that follower must still
+    take its tiles.  One that took the republished header for an old request never arrived; the
+    grid relaunched after the idle exit then completed the stale arrival count early, and the
+    tiles of the late followers came back unwritten (status 0, empty views).  On an idle GPU the
+    followers start in time, so this covers the path (64 workgroups, 100 launches) without
+    forcing the late start; it showed in the first launch of a fresh process on a busy one."""
+    s = codec.Server(workgroups=codec.SERVE_MAX_WORKGROUPS)
+    try:
+        data, off = T.mixed_records(4096, seed=0x63)  # 64 tiles: one per workgroup
+        exp = T.oracle_decode(data, off, T.DEC_PARSE)
+        d, r = to_dev(data, torch.uint8), to_dev(np.asarray(off, np.uint64), torch.int64)
+        rounds = 100
+        for _ in range(rounds):
+            assert_same_decode(s.decode(d, r, mode=T.DEC_PARSE).numpy(), exp)
+            s.quiesce()  # the grid leaves: the next request is the first of a new launch
+        assert s.stats()[1] == rounds
+    finally:
+        s.close()
