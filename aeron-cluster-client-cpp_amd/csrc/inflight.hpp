@@ -7,8 +7,9 @@
 //
 // Table: one 64-B header, then `capacity` (a power of two) slots of 64 B, linear probing from a
 // 64-bit hash of the zero-padded key and its length.
-//   slot  +0  u64 word   state << 62 | tag << 32 | record index (only while PENDING)
-//         +8  u64 ts
+//   slot  +0  u64 word   state << 62 | tag << 32 | record index (while PENDING) or the answered
+//                        bit (bit 0, while LIVE: a lookup_keys call has reported the entry's value)
+//         +8  u64 ts     the value: a send time (remember) or a number of deliveries (note_keys)
 //         +16 40 key bytes, zero-padded
 //         +56 u32 claim  smallest ack index of the running match call, 0xFFFFFFFF otherwise
 //         +60 u32 len
@@ -16,7 +17,7 @@
 // erased slots; sbe_inflight_rehash reclaims them), so "the first slot of the chain that is empty
 // or holds this key" is the same slot for every record of a key, whenever it walks.
 //
-// Both calls are two launches, one lane per record.
+// Every per-record call is two launches, one lane per record.
 //   remember, launch A   walk the chain.  EMPTY: 64-bit CAS to PENDING(tag, i).  PENDING with an
 //       equal tag: compare with the owner's key, read from the input arena; equal: atomicMin on the
 //       word hands the slot to the smaller index.  LIVE with an equal tag: compare with the stored
@@ -28,6 +29,15 @@
 //   match, launch A      find the LIVE slot of the id (EMPTY ends the chain), atomicMin(claim, i).
 //   match, launch B      the record whose index the claim holds is MATCHED: it reads ts and stores
 //       the ERASED word.  The others are UNMATCHED.
+//   note, launch A       remember's walk with keys anywhere in a buffer; every record that ends on
+//       a slot adds 1 to its value (an EMPTY slot's value is 0: init's memset, and no slot is reused).
+//   note, launch B       the owner of a PENDING slot writes key, len, claim and the LIVE word, not
+//       the value: NEW.  The others are AGAIN.  All read the finished sum.
+//   lookup, launch A     match's walk; atomicMin(claim, i) unless the entry is answered; the
+//       workspace word is the slot index with "was answered when found" in bit 31, and code[i]
+//       already holds the outcome of every record that found no entry.
+//   lookup, launch B     the record whose index the claim holds is FIRST: it reads the value, sets
+//       the answered bit and gives the claim back.  The others are REPEAT.
 // Within a launch no lane reads bytes another lane of that launch writes, except the state and
 // claim words, and those go through device-scope atomics: no fences or flags.  Which of two
 // colliding keys gets the earlier slot depends on timing; what a call reports does not.
@@ -46,7 +56,8 @@ constexpr uint32_t kInfWsSkipped = 0xFFFFFFF0u, kInfWsTooLong = 0xFFFFFFF1u, kIn
 struct InfHeader {
     uint64_t capacity, live, used;
     uint32_t tag_bits, magic;
-    uint64_t reserved[4];
+    uint64_t answered;  // live entries whose answered bit is set
+    uint64_t reserved[3];
 };
 struct InfSlot {
     uint64_t word, ts, key[5];
@@ -66,6 +77,7 @@ __device__ __forceinline__ uint64_t inf_word(uint64_t state, uint32_t tag, uint3
     return state << 62 | (uint64_t)tag << 32 | idx;
 }
 __device__ __forceinline__ uint32_t inf_word_tag(uint64_t w) { return (uint32_t)(w >> 32) & 0x3fffffffu; }
+constexpr uint64_t kInfAnswered = 1;  // bit 0 of a LIVE word
 
 // key bytes p[0, len), len <= 40, zero-padded into five words; reads no byte past p + len
 __device__ __forceinline__ void inf_load_key(const uint8_t* p, uint32_t len, InfKey& k) {
@@ -111,6 +123,41 @@ __device__ __forceinline__ bool inf_table(const uint8_t* table, uint64_t& cap, u
 }
 __device__ __forceinline__ uint64_t inf_ld(const uint64_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Launch A of an inserting call (remember, note): the slot of key k for record i, or kInfWsFull.
+// The first slot of the chain that is EMPTY (taken by CAS as PENDING(tag, i)), PENDING for an equal
+// key (atomicMin hands it to the smaller index) or LIVE with an equal key.  owner_key(j, o) loads
+// the key of record j of the running call into o; false: j is not a record that can own a slot.
+template <class OwnerKey>
+__device__ __forceinline__ uint32_t inf_claim_slot(uint8_t* table, uint64_t cap, uint64_t h, uint32_t tag, uint32_t i,
+                                                   const InfKey& k, const OwnerKey& owner_key) {
+    InfSlot* slots = reinterpret_cast<InfSlot*>(table + 64);
+    uint64_t s = h & (cap - 1);
+    for (uint64_t probe = 0; probe < cap; ++probe, s = (s + 1) & (cap - 1)) {
+        InfSlot* sl = slots + s;
+        uint64_t w = inf_ld(&sl->word);
+        if ((w >> 62) == kInfEmpty) {
+            unsigned long long seen = 0;
+            if (__hip_atomic_compare_exchange_strong(reinterpret_cast<unsigned long long*>(&sl->word), &seen,
+                                                     (unsigned long long)inf_word(kInfPending, tag, i), __ATOMIC_RELAXED,
+                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                return (uint32_t)s;
+            w = seen;  // another record took it first: look at what it holds
+        }
+        const uint64_t state = w >> 62;
+        if (state == kInfErased || inf_word_tag(w) != tag) continue;
+        if (state == kInfPending) {
+            InfKey o;
+            if (!owner_key((uint32_t)w, o) || !inf_key_eq(o, k)) continue;
+            __hip_atomic_fetch_min(reinterpret_cast<unsigned long long*>(&sl->word),
+                                   (unsigned long long)inf_word(kInfPending, tag, i), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            return (uint32_t)s;
+        }
+        if (inf_slot_eq(sl, k)) return (uint32_t)s;  // LIVE
+    }
+    return kInfWsFull;
 }
 
 __global__ __launch_bounds__(kWave) void inf_init_header(uint8_t* table, uint64_t capacity, uint32_t tag_bits) {
@@ -159,43 +206,12 @@ __global__ __launch_bounds__(kInfBlk) void inf_remember_find(InfRemArgs a) {
     inf_load_key(a.arena + a.key_off[i * a.stride], len, k);
     const uint64_t h = inf_hash(k);
     const uint32_t tag = inf_tag(h, tb);
-    InfSlot* slots = reinterpret_cast<InfSlot*>(a.table + 64);
-    uint32_t res = kInfWsFull;
-    uint64_t s = h & (cap - 1);
-    for (uint64_t probe = 0; probe < cap; ++probe, s = (s + 1) & (cap - 1)) {
-        InfSlot* sl = slots + s;
-        uint64_t w = inf_ld(&sl->word);
-        if ((w >> 62) == kInfEmpty) {
-            unsigned long long seen = 0;
-            if (__hip_atomic_compare_exchange_strong(reinterpret_cast<unsigned long long*>(&sl->word), &seen,
-                                                     (unsigned long long)inf_word(kInfPending, tag, (uint32_t)i),
-                                                     __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                res = (uint32_t)s;
-                break;
-            }
-            w = seen;  // another record took it first: look at what it holds
-        }
-        const uint64_t state = w >> 62;
-        if (state == kInfErased || inf_word_tag(w) != tag) continue;
-        if (state == kInfPending) {
-            const uint64_t j = (uint32_t)w;
-            const uint32_t jl = a.key_len[j * a.stride];
-            if (jl > SBE_INFLIGHT_KEY_MAX) continue;  // not a record that can own a slot
-            InfKey o;
-            inf_load_key(a.arena + a.key_off[j * a.stride], jl, o);
-            if (!inf_key_eq(o, k)) continue;
-            __hip_atomic_fetch_min(reinterpret_cast<unsigned long long*>(&sl->word),
-                                   (unsigned long long)inf_word(kInfPending, tag, (uint32_t)i), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            res = (uint32_t)s;
-            break;
-        }
-        if (inf_slot_eq(sl, k)) {  // LIVE
-            res = (uint32_t)s;
-            break;
-        }
-    }
-    a.ws[i] = res;
+    a.ws[i] = inf_claim_slot(a.table, cap, h, tag, (uint32_t)i, k, [&](uint64_t j, InfKey& o) {
+        const uint32_t jl = a.key_len[j * a.stride];
+        if (jl > SBE_INFLIGHT_KEY_MAX) return false;
+        inf_load_key(a.arena + a.key_off[j * a.stride], jl, o);
+        return true;
+    });
 }
 
 __global__ __launch_bounds__(kInfBlk) void inf_remember_commit(InfRemArgs a) {
@@ -299,7 +315,7 @@ __global__ __launch_bounds__(kInfBlk) void inf_match_find(InfMatchArgs a) {
 
 __global__ __launch_bounds__(kInfBlk) void inf_match_commit(InfMatchArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * kInfBlk + threadIdx.x;
-    bool matched = false, missed = false;
+    bool matched = false, missed = false, answered = false;
     if (i < a.n) {
         const uint32_t c = a.ws[i];
         uint32_t code = SBE_ACK_UNMATCHED;
@@ -314,7 +330,9 @@ __global__ __launch_bounds__(kInfBlk) void inf_match_commit(InfMatchArgs a) {
             if (sl->claim == (uint32_t)i) {
                 code = SBE_ACK_MATCHED;
                 base = sl->ts;
-                sl->word = inf_word(kInfErased, inf_word_tag(sl->word), 0);
+                const uint64_t w = sl->word;
+                answered = (w & kInfAnswered) != 0;
+                sl->word = inf_word(kInfErased, inf_word_tag(w), 0);
             } else {
                 base = a.ts[i];
             }
@@ -326,10 +344,12 @@ __global__ __launch_bounds__(kInfBlk) void inf_match_commit(InfMatchArgs a) {
     }
     const int nm = __syncthreads_count(matched);
     const int nu = __syncthreads_count(missed);
+    const int na = __syncthreads_count(answered);
     if (threadIdx.x == 0) {
         if (nm) {
             InfHeader* h = reinterpret_cast<InfHeader*>(a.table);
             atomicAdd(reinterpret_cast<unsigned long long*>(&h->live), (unsigned long long)(-(long long)nm));
+            if (na) atomicAdd(reinterpret_cast<unsigned long long*>(&h->answered), (unsigned long long)(-(long long)na));
             if (a.counts) atomicAdd(reinterpret_cast<unsigned long long*>(a.counts), (unsigned long long)nm);
         }
         if (nu && a.counts) atomicAdd(reinterpret_cast<unsigned long long*>(a.counts + 1), (unsigned long long)nu);
@@ -342,19 +362,20 @@ constexpr uint32_t kInfRehashBlocks = 2048;
 __global__ __launch_bounds__(kInfBlk) void inf_rehash_kernel(const uint8_t* src, uint8_t* dst) {
     uint64_t scap, dcap;
     uint32_t stb, dtb;
-    int moved = 0;
+    int moved = 0, marked = 0;
     if (inf_table(src, scap, stb) && inf_table(dst, dcap, dtb)) {
         const InfSlot* from = reinterpret_cast<const InfSlot*>(src + 64);
         InfSlot* to = reinterpret_cast<InfSlot*>(dst + 64);
         for (uint64_t q = (uint64_t)blockIdx.x * kInfBlk + threadIdx.x; q < scap; q += (uint64_t)gridDim.x * kInfBlk) {
             const InfSlot* f = from + q;
-            if ((f->word >> 62) != kInfLive) continue;
+            const uint64_t fw = f->word;
+            if ((fw >> 62) != kInfLive) continue;
             InfKey k;
 #pragma unroll
             for (int j = 0; j < 5; ++j) k.w[j] = f->key[j];
             k.len = f->len;
             const uint64_t h = inf_hash(k);
-            const unsigned long long live = inf_word(kInfLive, inf_tag(h, dtb), 0);
+            const unsigned long long live = inf_word(kInfLive, inf_tag(h, dtb), (uint32_t)(fw & kInfAnswered));
             uint64_t s = h & (dcap - 1);
             for (uint64_t probe = 0; probe < dcap; ++probe, s = (s + 1) & (dcap - 1)) {
                 InfSlot* t = to + s;
@@ -369,19 +390,228 @@ __global__ __launch_bounds__(kInfBlk) void inf_rehash_kernel(const uint8_t* src,
                 t->claim = kInfNoClaim;
                 t->len = k.len;
                 ++moved;
+                marked += (int)(fw & kInfAnswered);
                 break;
             }
         }
     }
     // per-thread counts summed over the block: one pair of atomics per workgroup
-    __shared__ int total;
-    if (threadIdx.x == 0) total = 0;
+    __shared__ int total, total_marked;
+    if (threadIdx.x == 0) total = total_marked = 0;
     __syncthreads();
     if (moved) atomicAdd(&total, moved);
+    if (marked) atomicAdd(&total_marked, marked);
     __syncthreads();
     if (threadIdx.x == 0 && total) {
         InfHeader* h = reinterpret_cast<InfHeader*>(dst);
         atomicAdd(reinterpret_cast<unsigned long long*>(&h->live), (unsigned long long)total);
         atomicAdd(reinterpret_cast<unsigned long long*>(&h->used), (unsigned long long)total);
+        if (total_marked) atomicAdd(reinterpret_cast<unsigned long long*>(&h->answered), (unsigned long long)total_marked);
     }
+}
+
+// ---- keys anywhere in a buffer: note_keys (test-and-insert that counts) and lookup_keys ----
+
+struct InfKeysArgs {
+    uint8_t* table;
+    const uint8_t* buf;
+    uint64_t buf_bytes;
+    const uint64_t* key_pos;
+    const uint32_t* key_len;
+    uint64_t n;
+    uint8_t* code;
+    uint32_t* count;   // note
+    uint64_t* value;   // lookup
+    uint64_t* totals;  // or null
+    uint32_t* ws;
+};
+
+// key i clamped into [0, buf_bytes): no byte at or past buf_bytes is read
+__device__ __forceinline__ void inf_key_range(const InfKeysArgs& a, uint64_t i, uint64_t& pos, uint32_t& len) {
+    const uint64_t p = a.key_pos[i];
+    pos = p <= a.buf_bytes ? p : a.buf_bytes;
+    const uint64_t room = a.buf_bytes - pos;
+    const uint32_t l = a.key_len[i];
+    len = l <= room ? l : (uint32_t)room;
+}
+
+__global__ __launch_bounds__(kInfBlk) void inf_note_find(InfKeysArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * kInfBlk + threadIdx.x;
+    if (i >= a.n) return;
+    if (a.key_len[i] == SBE_NO_KEY) {
+        a.ws[i] = kInfWsNone;
+        return;
+    }
+    uint64_t pos;
+    uint32_t len;
+    inf_key_range(a, i, pos, len);
+    if (len > SBE_INFLIGHT_KEY_MAX) {
+        a.ws[i] = kInfWsTooLong;
+        return;
+    }
+    uint64_t cap;
+    uint32_t tb;
+    if (!inf_table(a.table, cap, tb)) {
+        a.ws[i] = kInfWsFull;
+        return;
+    }
+    InfKey k;
+    inf_load_key(a.buf + pos, len, k);
+    const uint64_t h = inf_hash(k);
+    const uint32_t tag = inf_tag(h, tb);
+    const uint32_t res = inf_claim_slot(a.table, cap, h, tag, (uint32_t)i, k, [&](uint64_t j, InfKey& o) {
+        if (j >= a.n || a.key_len[j] == SBE_NO_KEY) return false;
+        uint64_t jp;
+        uint32_t jl;
+        inf_key_range(a, j, jp, jl);
+        if (jl > SBE_INFLIGHT_KEY_MAX) return false;
+        inf_load_key(a.buf + jp, jl, o);
+        return true;
+    });
+    if (res != kInfWsFull)  // one more delivery of this slot's key
+        __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(&reinterpret_cast<InfSlot*>(a.table + 64)[res].ts), 1ull,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    a.ws[i] = res;
+}
+
+__global__ __launch_bounds__(kInfBlk) void inf_note_commit(InfKeysArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * kInfBlk + threadIdx.x;
+    bool fresh = false, again = false;
+    if (i < a.n) {
+        const uint32_t c = a.ws[i];
+        uint32_t code = SBE_DLV_NONE, count = 0;
+        if (c == kInfWsNone) {
+            code = SBE_DLV_NONE;
+        } else if (c == kInfWsTooLong) {
+            code = SBE_DLV_LONG;
+        } else if (c == kInfWsFull) {
+            code = SBE_DLV_FULL;
+        } else {
+            InfSlot* sl = reinterpret_cast<InfSlot*>(a.table + 64) + c;
+            const uint64_t w = inf_ld(&sl->word);
+            code = SBE_DLV_AGAIN;
+            count = (uint32_t)(sl->ts - 1);  // launch A finished every add
+            if ((w >> 62) == kInfPending && (uint32_t)w == (uint32_t)i) {
+                uint64_t pos;
+                uint32_t len;
+                inf_key_range(a, i, pos, len);
+                InfKey k;
+                inf_load_key(a.buf + pos, len, k);
+#pragma unroll
+                for (int j = 0; j < 5; ++j) sl->key[j] = k.w[j];
+                sl->claim = kInfNoClaim;
+                sl->len = k.len;
+                __hip_atomic_store(&sl->word, inf_word(kInfLive, inf_word_tag(w), 0), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+                code = SBE_DLV_NEW;
+            }
+        }
+        a.code[i] = (uint8_t)code;
+        a.count[i] = count;
+        fresh = code == SBE_DLV_NEW;
+        again = code == SBE_DLV_AGAIN;
+    }
+    const int nf = __syncthreads_count(fresh);
+    const int na = __syncthreads_count(again);
+    if (threadIdx.x == 0) {
+        if (nf) {
+            InfHeader* h = reinterpret_cast<InfHeader*>(a.table);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&h->live), (unsigned long long)nf);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&h->used), (unsigned long long)nf);
+            if (a.totals) atomicAdd(reinterpret_cast<unsigned long long*>(a.totals), (unsigned long long)nf);
+        }
+        if (na && a.totals) atomicAdd(reinterpret_cast<unsigned long long*>(a.totals + 1), (unsigned long long)na);
+    }
+}
+
+constexpr uint32_t kInfWsAnswered = 0x80000000u;  // slot indices are below 2^31
+
+__global__ __launch_bounds__(kInfBlk) void inf_lookup_find(InfKeysArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * kInfBlk + threadIdx.x;
+    if (i >= a.n) return;
+    uint32_t code = SBE_SENT_UNKNOWN, res = 0;
+    if (a.key_len[i] == SBE_NO_KEY) {
+        code = SBE_SENT_NONE;
+    } else {
+        uint64_t pos, cap;
+        uint32_t len, tb;
+        inf_key_range(a, i, pos, len);
+        if (len > SBE_INFLIGHT_KEY_MAX) {
+            code = SBE_SENT_LONG;
+        } else if (inf_table(a.table, cap, tb)) {
+            InfKey k;
+            inf_load_key(a.buf + pos, len, k);
+            const uint64_t h = inf_hash(k);
+            const uint32_t tag = inf_tag(h, tb);
+            InfSlot* slots = reinterpret_cast<InfSlot*>(a.table + 64);
+            uint64_t s = h & (cap - 1);
+            for (uint64_t probe = 0; probe < cap; ++probe, s = (s + 1) & (cap - 1)) {
+                InfSlot* sl = slots + s;
+                const uint64_t w = sl->word;  // launch A of a lookup writes no word
+                const uint64_t state = w >> 62;
+                if (state == kInfEmpty) break;
+                if (state != kInfLive || inf_word_tag(w) != tag || !inf_slot_eq(sl, k)) continue;
+                code = SBE_SENT_REPEAT;  // launch B decides between FIRST and REPEAT
+                res = (uint32_t)s;
+                if (w & kInfAnswered)
+                    res |= kInfWsAnswered;
+                else
+                    __hip_atomic_fetch_min(&sl->claim, (uint32_t)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                break;
+            }
+        }
+    }
+    a.code[i] = (uint8_t)code;
+    a.ws[i] = res;
+}
+
+__global__ __launch_bounds__(kInfBlk) void inf_lookup_commit(InfKeysArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * kInfBlk + threadIdx.x;
+    bool first = false, repeat = false, unknown = false;
+    if (i < a.n) {
+        uint32_t code = a.code[i];
+        uint64_t value = 0;
+        if (code == SBE_SENT_REPEAT) {
+            const uint32_t c = a.ws[i];
+            // an entry answered before the call took no claim; otherwise the claim is the smallest
+            // index of the call, and only that lane writes the slot
+            if (!(c & kInfWsAnswered)) {
+                InfSlot* sl = reinterpret_cast<InfSlot*>(a.table + 64) + c;
+                if (__hip_atomic_load(&sl->claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)i) {
+                    code = SBE_SENT_FIRST;
+                    value = sl->ts;
+                    sl->word |= kInfAnswered;
+                    __hip_atomic_store(&sl->claim, kInfNoClaim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+            a.code[i] = (uint8_t)code;
+        }
+        a.value[i] = value;
+        first = code == SBE_SENT_FIRST;
+        repeat = code == SBE_SENT_REPEAT;
+        unknown = code == SBE_SENT_UNKNOWN || code == SBE_SENT_LONG;
+    }
+    const int nf = __syncthreads_count(first);
+    const int nr = __syncthreads_count(repeat);
+    const int nu = __syncthreads_count(unknown);
+    if (threadIdx.x == 0) {
+        if (nf) atomicAdd(reinterpret_cast<unsigned long long*>(&reinterpret_cast<InfHeader*>(a.table)->answered),
+                          (unsigned long long)nf);
+        if (a.totals) {
+            if (nf) atomicAdd(reinterpret_cast<unsigned long long*>(a.totals), (unsigned long long)nf);
+            if (nr) atomicAdd(reinterpret_cast<unsigned long long*>(a.totals + 1), (unsigned long long)nr);
+            if (nu) atomicAdd(reinterpret_cast<unsigned long long*>(a.totals + 2), (unsigned long long)nu);
+        }
+    }
+}
+
+// The value of every LIVE slot back to one delivery (clear_duplicate_tracking: the per-id counts of
+// record_duplicate_delivery start again, so the next redelivery of a known id reports 1).
+__global__ __launch_bounds__(kInfBlk) void inf_reset_values_kernel(uint8_t* table) {
+    uint64_t cap;
+    uint32_t tb;
+    if (!inf_table(table, cap, tb)) return;
+    InfSlot* slots = reinterpret_cast<InfSlot*>(table + 64);
+    for (uint64_t q = (uint64_t)blockIdx.x * kInfBlk + threadIdx.x; q < cap; q += (uint64_t)gridDim.x * kInfBlk)
+        if ((slots[q].word >> 62) == kInfLive) slots[q].ts = 1;
 }

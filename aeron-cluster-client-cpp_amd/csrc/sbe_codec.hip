@@ -4361,6 +4361,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 #include "commit_emit.hpp"
 #include "commit_fallback.hpp"
 #include "json_paths.hpp"
+#include "delivery_keys.hpp"
 
 }  // namespace
 
@@ -5181,6 +5182,84 @@ int sbe_inflight_rehash(const void* src, void* dst, void* stream) {
         return SBE_EINVAL;
     hipLaunchKernelGGL(inf_rehash_kernel, dim3(kInfRehashBlocks), dim3(kInfBlk), 0, s,
                        reinterpret_cast<const uint8_t*>(src), reinterpret_cast<uint8_t*>(dst));
+    return record_hip(hipGetLastError());
+}
+
+namespace {
+// the checks sbe_inflight_note_keys and sbe_inflight_lookup_keys share; `result` is count / value
+int inf_keys_check(const void* table, const uint8_t* buf, const uint64_t* key_pos, const uint32_t* key_len, uint64_t n,
+                   const uint8_t* code, const void* result, uint32_t result_mask, const uint64_t* totals,
+                   const void* workspace, size_t workspace_bytes) {
+    if (!table || misaligned(table, 63) || n >= (1ull << 32) || misaligned(totals, 7)) return SBE_EINVAL;
+    if (n == 0) return SBE_OK;
+    if (!buf || !key_pos || !key_len || !code || !result || !workspace) return SBE_EINVAL;
+    if (misaligned(key_pos, 7) || misaligned(key_len, 3) || misaligned(result, result_mask) || misaligned(workspace, 3))
+        return SBE_EINVAL;
+    return workspace_bytes < sbe_inflight_workspace_size(n) ? SBE_ENOSPC : SBE_OK;
+}
+}  // namespace
+
+int sbe_inflight_note_keys(void* table, const uint8_t* buf, uint64_t buf_bytes, const uint64_t* key_pos,
+                           const uint32_t* key_len, uint64_t n, uint8_t* code, uint32_t* count, uint64_t* totals,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = inf_keys_check(table, buf, key_pos, key_len, n, code, count, 3, totals, workspace, workspace_bytes))
+        return rc;
+    if (totals)
+        if (const int rc = record_hip(hipMemsetAsync(totals, 0, 16, s))) return rc;
+    if (n == 0) return SBE_OK;
+    InfKeysArgs a{reinterpret_cast<uint8_t*>(table), buf, buf_bytes, key_pos, key_len, n, code, count, nullptr, totals,
+                  reinterpret_cast<uint32_t*>(workspace)};
+    const uint32_t blocks = (uint32_t)((n + kInfBlk - 1) / kInfBlk);
+    hipLaunchKernelGGL(inf_note_find, dim3(blocks), dim3(kInfBlk), 0, s, a);
+    hipLaunchKernelGGL(inf_note_commit, dim3(blocks), dim3(kInfBlk), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+int sbe_inflight_lookup_keys(void* table, const uint8_t* buf, uint64_t buf_bytes, const uint64_t* key_pos,
+                             const uint32_t* key_len, uint64_t n, uint8_t* code, uint64_t* value, uint64_t* totals,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = inf_keys_check(table, buf, key_pos, key_len, n, code, value, 7, totals, workspace, workspace_bytes))
+        return rc;
+    if (totals)
+        if (const int rc = record_hip(hipMemsetAsync(totals, 0, 24, s))) return rc;
+    if (n == 0) return SBE_OK;
+    InfKeysArgs a{reinterpret_cast<uint8_t*>(table), buf, buf_bytes, key_pos, key_len, n, code, nullptr, value, totals,
+                  reinterpret_cast<uint32_t*>(workspace)};
+    const uint32_t blocks = (uint32_t)((n + kInfBlk - 1) / kInfBlk);
+    hipLaunchKernelGGL(inf_lookup_find, dim3(blocks), dim3(kInfBlk), 0, s, a);
+    hipLaunchKernelGGL(inf_lookup_commit, dim3(blocks), dim3(kInfBlk), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+int sbe_inflight_reset_values(void* table, void* stream) {
+    if (!table || misaligned(table, 63)) return SBE_EINVAL;
+    hipLaunchKernelGGL(inf_reset_values_kernel, dim3(kInfRehashBlocks), dim3(kInfBlk), 0,
+                       reinterpret_cast<hipStream_t>(stream), reinterpret_cast<uint8_t*>(table));
+    return record_hip(hipGetLastError());
+}
+
+int sbe_delivery_keys(const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec, const uint8_t* select,
+                      const sbe_json_out* ids, const sbe_delivery_key_out* out, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!out || !out->totals || misaligned(out->totals, 7) || n >= (1ull << 32)) return SBE_EINVAL;
+    if (n && (!rec_off || !dec || !dec->status || !dec->view_off || !dec->view_len || !ids || !ids->doc ||
+              !ids->root_kind || !ids->kind || !ids->off || !ids->len || !out->msg_pos || !out->msg_len ||
+              !out->coid_pos || !out->coid_len || !out->coid_kind || !out->oid_pos || !out->oid_len || !out->oid_kind ||
+              !out->selected))
+        return SBE_EINVAL;
+    if (n && (misaligned(rec_off, 7) || misaligned(dec->view_off, 3) || misaligned(dec->view_len, 3) ||
+              misaligned(ids->off, 3) || misaligned(ids->len, 3) || misaligned(out->msg_pos, 7) ||
+              misaligned(out->msg_len, 3) || misaligned(out->coid_pos, 7) || misaligned(out->coid_len, 3) ||
+              misaligned(out->oid_pos, 7) || misaligned(out->oid_len, 3)))
+        return SBE_EINVAL;
+    if (const int rc = record_hip(hipMemsetAsync(out->totals, 0, 16, s))) return rc;
+    if (n == 0) return SBE_OK;
+    DkArgs a{rec_off,       n,           dec->status,   dec->view_off, dec->view_len,  select,        ids->doc,
+             ids->root_kind, ids->kind,  ids->off,      ids->len,      out->msg_pos,   out->msg_len,  out->coid_pos,
+             out->coid_len, out->coid_kind, out->oid_pos, out->oid_len, out->oid_kind, out->selected, out->totals};
+    hipLaunchKernelGGL(sbe_delivery_keys_kernel, dim3((uint32_t)((n + kDkBlk - 1) / kDkBlk)), dim3(kDkBlk), 0, s, a);
     return record_hip(hipGetLastError());
 }
 

@@ -29,6 +29,8 @@
 #include <sstream>
 #include <stdexcept>
 #include <thread>
+#include <unordered_map>
+#include <unordered_set>
 
 #include "sbecodec.h"
 #include "workers.hpp"
@@ -3072,26 +3074,33 @@ void MessageHandler::on_egress_batch(const std::uint8_t* data, const std::uint64
 // ======================================================================================
 // AckCorrelator
 // ======================================================================================
-struct AckCorrelator::Impl {
-    hipStream_t stream = nullptr;
-    DevBuf table, in, out;  // the table; staged inputs; descriptors / results / workspace
+namespace {
+// One sbe_inflight_* table in device memory that grows by rehash.
+struct InfTable {
+    DevBuf mem;
     uint64_t cap = 0, used_bound = 0, rehashes = 0;
     uint32_t tag_bits = 0;
-    std::unordered_map<std::string, uint64_t> long_keys;  // keys the table cannot hold
-    std::vector<uint8_t> stage;
 
-    uint8_t* tbl() const { return reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(table.p) + 63) & ~uintptr_t(63)); }
-    static size_t al(size_t v) { return (v + 63) & ~size_t(63); }
-    void sync() { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
-    void header(uint64_t h[3]) {
-        hip_check(hipMemcpyAsync(h, tbl(), 24, hipMemcpyDeviceToHost, stream), "D2H");
-        sync();
+    static uint8_t* aligned(const DevBuf& b) {
+        return reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(b.p) + 63) & ~uintptr_t(63));
+    }
+    uint8_t* p() const { return aligned(mem); }
+    void init(uint64_t c, uint32_t tb, hipStream_t s) {
+        cap = c;
+        tag_bits = tb;
+        mem.need(sbe_inflight_table_size(c) + 64);
+        if (sbe_inflight_init(p(), sbe_inflight_table_size(c), c, tb, s) != SBE_OK) fail("sbe_inflight_init");
+    }
+    // capacity, live, used, tag bits, answered
+    void header(uint64_t h[5], hipStream_t s) const {
+        hip_check(hipMemcpyAsync(h, p(), 40, hipMemcpyDeviceToHost, s), "D2H");
+        hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
     }
     // room for n more inserts below half the capacity, by rehash when needed
-    void reserve(uint64_t n) {
+    void reserve(uint64_t n, hipStream_t s) {
         if (used_bound + n <= cap / 2) return;
-        uint64_t h[3];
-        header(h);
+        uint64_t h[5];
+        header(h, s);
         used_bound = h[2];
         if (used_bound + n <= cap / 2) return;
         uint64_t ncap = cap;
@@ -3099,16 +3108,29 @@ struct AckCorrelator::Impl {
         if (ncap > (1ull << 31)) throw std::runtime_error("sbecodec: the in-flight table cannot grow past 2^31 slots");
         DevBuf fresh;
         fresh.need(sbe_inflight_table_size(ncap) + 64);
-        uint8_t* dst = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(fresh.p) + 63) & ~uintptr_t(63));
-        if (sbe_inflight_init(dst, sbe_inflight_table_size(ncap), ncap, tag_bits, stream) != SBE_OK) fail("sbe_inflight_init");
-        if (sbe_inflight_rehash(tbl(), dst, stream) != SBE_OK) fail("sbe_inflight_rehash");
-        sync();
-        std::swap(table.p, fresh.p);
-        std::swap(table.cap, fresh.cap);
+        uint8_t* dst = aligned(fresh);
+        if (sbe_inflight_init(dst, sbe_inflight_table_size(ncap), ncap, tag_bits, s) != SBE_OK) fail("sbe_inflight_init");
+        if (sbe_inflight_rehash(p(), dst, s) != SBE_OK) fail("sbe_inflight_rehash");
+        hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        std::swap(mem.p, fresh.p);
+        std::swap(mem.cap, fresh.cap);
         cap = ncap;
         used_bound = h[1];
         ++rehashes;
     }
+};
+}  // namespace
+
+struct AckCorrelator::Impl {
+    hipStream_t stream = nullptr;
+    InfTable table;
+    DevBuf in, out;  // staged inputs; descriptors / results / workspace
+    std::unordered_map<std::string, uint64_t> long_keys;  // keys the table cannot hold
+    std::vector<uint8_t> stage;
+
+    uint8_t* tbl() const { return table.p(); }
+    static size_t al(size_t v) { return (v + 63) & ~size_t(63); }
+    void sync() { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
 };
 
 AckCorrelator::AckCorrelator(std::uint64_t initial_capacity, std::uint32_t tag_bits) : impl_(new Impl) {
@@ -3116,10 +3138,7 @@ AckCorrelator::AckCorrelator(std::uint64_t initial_capacity, std::uint32_t tag_b
     const size_t bytes = sbe_inflight_table_size(initial_capacity);
     if (!bytes || tag_bits > 30) throw std::invalid_argument("AckCorrelator: capacity must be a power of two in 64 .. 2^31");
     hip_check(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking), "hipStreamCreate");
-    m.cap = initial_capacity;
-    m.tag_bits = tag_bits;
-    m.table.need(bytes + 64);
-    if (sbe_inflight_init(m.tbl(), bytes, m.cap, tag_bits, m.stream) != SBE_OK) fail("sbe_inflight_init");
+    m.table.init(initial_capacity, tag_bits, m.stream);
     m.sync();
 }
 
@@ -3130,11 +3149,11 @@ AckCorrelator::~AckCorrelator() {
     }
 }
 
-std::uint64_t AckCorrelator::capacity() const { return impl_->cap; }
-std::uint64_t AckCorrelator::rehashes() const { return impl_->rehashes; }
+std::uint64_t AckCorrelator::capacity() const { return impl_->table.cap; }
+std::uint64_t AckCorrelator::rehashes() const { return impl_->table.rehashes; }
 std::size_t AckCorrelator::size() const {
-    uint64_t h[3];
-    impl_->header(h);
+    uint64_t h[5];
+    impl_->table.header(h, impl_->stream);
     return (size_t)h[1] + impl_->long_keys.size();
 }
 
@@ -3174,7 +3193,7 @@ void AckCorrelator::remember_batch(const std::vector<std::string>& uuids, const 
     }
     if (!k) return;
     if (bytes > 0xffffffffull) throw std::invalid_argument("AckCorrelator::remember_batch: more than 4 GiB of keys");
-    m.reserve(k);
+    m.table.reserve(k, m.stream);
     const size_t wsb = sbe_inflight_workspace_size(k);
     m.in.need(total);
     m.out.need(wsb);
@@ -3186,7 +3205,7 @@ void AckCorrelator::remember_batch(const std::vector<std::string>& uuids, const 
                               m.stream) != SBE_OK)
         fail("sbe_inflight_remember");
     m.sync();  // the staging buffer is reused by the next call
-    m.used_bound += k;
+    m.table.used_bound += k;
 }
 
 namespace {
@@ -3565,6 +3584,387 @@ OrderIds extract_order_ids(const ParseResult& result) {
     if (!order_callback_looks(result) || result.payload.empty()) return {};
     const std::vector<std::string> docs{result.payload};
     return order_ids_of(extract_json_documents(docs, order_id_paths()), 0);
+}
+
+// ======================================================================================
+// DeliveryTracker (examples/pubsub_reconnect_test.cpp:625-716)
+// ======================================================================================
+namespace {
+inline size_t al64(size_t v) { return (v + 63) & ~size_t(63); }
+
+// Device layout of the three table calls' results (64-B aligned pieces).
+struct TrackLayout {
+    size_t mcode, mcount, ccode, ccount, scode, sval, ws, total;
+    explicit TrackLayout(size_t n) {
+        size_t p = 0;
+        mcode = p, p = al64(p + n);
+        mcount = p, p = al64(p + 4 * n);
+        ccode = p, p = al64(p + n);
+        ccount = p, p = al64(p + 4 * n);
+        scode = p, p = al64(p + n);
+        sval = p, p = al64(p + 8 * n);
+        ws = p, p = al64(p + sbe_inflight_workspace_size(n));
+        total = p;
+    }
+};
+
+struct TrackResults {
+    std::vector<uint8_t> mcode, ccode, scode;
+    std::vector<uint32_t> mcount;
+    std::vector<uint64_t> sval;
+};
+}  // namespace
+
+struct DeliveryTracker::Impl {
+    struct LongSent {
+        uint64_t ts;
+        bool answered;
+    };
+    hipStream_t stream = nullptr;
+    InfTable msgs, clients, sends;
+    DevBuf in, out;
+    std::vector<uint8_t> stage;
+    uint64_t received = 0;
+    // ids the tables cannot hold
+    std::unordered_map<std::string, uint64_t> long_msgs;  // message id -> deliveries
+    std::unordered_set<std::string> long_clients;
+    std::unordered_map<std::string, LongSent> long_sent;
+    size_t long_answered = 0;
+
+    void sync() { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
+
+    // note (message ids), note (client ids), lookup (sent) over keys that lie in a device buffer;
+    // `res` is device memory of TrackLayout(n).total bytes
+    void track(const uint8_t* buf, uint64_t buf_bytes, const uint64_t* mpos, const uint32_t* mlen, const uint64_t* cpos,
+               const uint32_t* clen, size_t n, uint8_t* res, TrackResults& r) {
+        const TrackLayout L(n);
+        const size_t wsb = sbe_inflight_workspace_size(n);
+        msgs.reserve(n, stream);
+        clients.reserve(n, stream);
+        if (sbe_inflight_note_keys(msgs.p(), buf, buf_bytes, mpos, mlen, n, res + L.mcode,
+                                   reinterpret_cast<uint32_t*>(res + L.mcount), nullptr, res + L.ws, wsb, stream) != SBE_OK)
+            fail("sbe_inflight_note_keys");
+        if (sbe_inflight_note_keys(clients.p(), buf, buf_bytes, cpos, clen, n, res + L.ccode,
+                                   reinterpret_cast<uint32_t*>(res + L.ccount), nullptr, res + L.ws, wsb, stream) != SBE_OK)
+            fail("sbe_inflight_note_keys");
+        if (sbe_inflight_lookup_keys(sends.p(), buf, buf_bytes, cpos, clen, n, res + L.scode,
+                                     reinterpret_cast<uint64_t*>(res + L.sval), nullptr, res + L.ws, wsb, stream) != SBE_OK)
+            fail("sbe_inflight_lookup_keys");
+        msgs.used_bound += n;
+        clients.used_bound += n;
+        r.mcode.resize(n);
+        r.ccode.resize(n);
+        r.scode.resize(n);
+        r.mcount.resize(n);
+        r.sval.resize(n);
+        auto back = [&](void* dst, size_t off, size_t len) {
+            hip_check(hipMemcpyAsync(dst, res + off, len, hipMemcpyDeviceToHost, stream), "D2H");
+        };
+        back(r.mcode.data(), L.mcode, n);
+        back(r.mcount.data(), L.mcount, 4 * n);
+        back(r.ccode.data(), L.ccode, n);
+        back(r.scode.data(), L.scode, n);
+        back(r.sval.data(), L.sval, 8 * n);
+        sync();
+    }
+
+    // the callback's bookkeeping for one selected record from its three codes; ids over the key
+    // limit go through the host sets
+    void settle(Delivery& d, std::string_view mid, const TrackResults& r, size_t i, uint64_t now_ns) {
+        bool again = r.mcode[i] == SBE_DLV_AGAIN;
+        d.redeliveries = again ? r.mcount[i] : 0;
+        if (mid.size() > SBE_INFLIGHT_KEY_MAX) {
+            uint64_t& c = long_msgs[std::string(mid)];
+            again = c > 0;
+            d.redeliveries = (uint32_t)c;  // on_batch writes the batch's last value afterwards
+            ++c;
+        }
+        d.already_processed = again;
+        if (!again) ++received;
+        bool client_again = r.ccode[i] == SBE_DLV_AGAIN;
+        if (d.client_order_id.size() > SBE_INFLIGHT_KEY_MAX) client_again = !long_clients.insert(d.client_order_id).second;
+        d.duplicate_client_order = client_again && !again;
+        if (d.client_order_id.size() > SBE_INFLIGHT_KEY_MAX) {
+            auto it = long_sent.find(d.client_order_id);
+            d.was_sent = it != long_sent.end();
+            if (d.was_sent && !it->second.answered) {
+                it->second.answered = true;
+                ++long_answered;
+                d.latency_recorded = true;
+                d.latency_ns = (int64_t)now_ns - (int64_t)it->second.ts;
+            }
+        } else {
+            d.was_sent = r.scode[i] == SBE_SENT_FIRST || r.scode[i] == SBE_SENT_REPEAT;
+            d.latency_recorded = r.scode[i] == SBE_SENT_FIRST;
+            if (d.latency_recorded) d.latency_ns = (int64_t)now_ns - (int64_t)r.sval[i];
+        }
+    }
+};
+
+DeliveryTracker::DeliveryTracker(std::uint64_t initial_capacity, std::uint32_t tag_bits) : impl_(new Impl) {
+    Impl& m = *impl_;
+    if (!sbe_inflight_table_size(initial_capacity) || tag_bits > 30)
+        throw std::invalid_argument("DeliveryTracker: capacity must be a power of two in 64 .. 2^31");
+    hip_check(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking), "hipStreamCreate");
+    for (InfTable* t : {&m.msgs, &m.clients, &m.sends}) t->init(initial_capacity, tag_bits, m.stream);
+    m.sync();
+}
+
+DeliveryTracker::~DeliveryTracker() {
+    if (impl_->stream) {
+        (void)hipStreamSynchronize(impl_->stream);
+        (void)hipStreamDestroy(impl_->stream);
+    }
+}
+
+std::uint64_t DeliveryTracker::messages_received() const { return impl_->received; }
+std::uint64_t DeliveryTracker::rehashes() const { return impl_->msgs.rehashes + impl_->clients.rehashes + impl_->sends.rehashes; }
+std::size_t DeliveryTracker::sent() const {
+    uint64_t h[5];
+    impl_->sends.header(h, impl_->stream);
+    return (size_t)h[1] + impl_->long_sent.size();
+}
+std::size_t DeliveryTracker::received() const {
+    uint64_t h[5];
+    impl_->clients.header(h, impl_->stream);
+    return (size_t)h[1] + impl_->long_clients.size();
+}
+std::size_t DeliveryTracker::missing() const {
+    uint64_t h[5];
+    impl_->sends.header(h, impl_->stream);
+    return (size_t)(h[1] - h[4]) + impl_->long_sent.size() - impl_->long_answered;
+}
+std::size_t DeliveryTracker::extra() const {
+    uint64_t h[5];
+    impl_->sends.header(h, impl_->stream);
+    return received() - (size_t)h[4] - impl_->long_answered;
+}
+
+void DeliveryTracker::clear_duplicate_tracking() {
+    Impl& m = *impl_;
+    if (sbe_inflight_reset_values(m.msgs.p(), m.stream) != SBE_OK) fail("sbe_inflight_reset_values");
+    m.sync();
+    for (auto& kv : m.long_msgs) kv.second = 1;
+}
+
+void DeliveryTracker::note_sent(const std::vector<std::string>& ids, std::uint64_t ts_ns) {
+    Impl& m = *impl_;
+    // staged: key_off [k] u32, key_len [k] u32, key bytes
+    size_t k = 0, bytes = 0;
+    for (const std::string& u : ids) {
+        if (u.size() <= SBE_INFLIGHT_KEY_MAX) {
+            ++k;
+            bytes += u.size();
+        } else {
+            m.long_sent.emplace(u, Impl::LongSent{ts_ns, false});
+        }
+    }
+    if (!k) return;
+    if (bytes > 0xffffffffull) throw std::invalid_argument("DeliveryTracker::note_sent: more than 4 GiB of ids");
+    const size_t o_len = 4 * k, o_key = 8 * k, total = o_key + bytes + 16;
+    m.stage.resize(total);
+    uint32_t* off = reinterpret_cast<uint32_t*>(m.stage.data());
+    uint32_t* len = reinterpret_cast<uint32_t*>(m.stage.data() + o_len);
+    size_t j = 0, pos = 0;
+    for (const std::string& u : ids) {
+        if (u.size() > SBE_INFLIGHT_KEY_MAX) continue;
+        off[j] = (uint32_t)pos;
+        len[j] = (uint32_t)u.size();
+        std::memcpy(m.stage.data() + o_key + pos, u.data(), u.size());
+        pos += u.size();
+        ++j;
+    }
+    m.sends.reserve(k, m.stream);
+    const size_t wsb = sbe_inflight_workspace_size(k);
+    m.in.need(total);
+    m.out.need(wsb);
+    hip_check(hipMemcpyAsync(m.in.p, m.stage.data(), total, hipMemcpyHostToDevice, m.stream), "H2D");
+    if (sbe_inflight_remember(m.sends.p(), m.in.b() + o_key, reinterpret_cast<const uint32_t*>(m.in.p),
+                              reinterpret_cast<const uint32_t*>(m.in.b() + o_len), 1, nullptr, ts_ns, nullptr, k, nullptr,
+                              m.out.p, wsb, m.stream) != SBE_OK)
+        fail("sbe_inflight_remember");
+    m.sync();  // the staging buffer is reused by the next call
+    m.sends.used_bound += k;
+}
+
+Delivery DeliveryTracker::on_message(const ParseResult& result, std::uint64_t now_ns) {
+    Impl& m = *impl_;
+    Delivery d;
+    d.selected = order_callback_looks(result);
+    if (!d.selected) return d;
+    OrderIds ids = extract_order_ids(result);
+    d.client_order_id = std::move(ids.client_order_id);
+    d.order_id = std::move(ids.order_id);
+    // a one-record batch of keys: the two ids back to back; ids the tables cannot hold get no key
+    const std::string& mid = result.message_id;
+    const std::string& cid = d.client_order_id;
+    const size_t o_cpos = 8, o_mlen = 16, o_clen = 20, o_key = 64, total = o_key + mid.size() + cid.size() + 16;
+    m.stage.assign(total, 0);
+    const uint64_t mpos = 0, cpos = mid.size();
+    const uint32_t mlen = mid.empty() || mid.size() > SBE_INFLIGHT_KEY_MAX ? SBE_NO_KEY : (uint32_t)mid.size();
+    const uint32_t clen = cid.empty() || cid.size() > SBE_INFLIGHT_KEY_MAX ? SBE_NO_KEY : (uint32_t)cid.size();
+    std::memcpy(m.stage.data(), &mpos, 8);
+    std::memcpy(m.stage.data() + o_cpos, &cpos, 8);
+    std::memcpy(m.stage.data() + o_mlen, &mlen, 4);
+    std::memcpy(m.stage.data() + o_clen, &clen, 4);
+    std::memcpy(m.stage.data() + o_key, mid.data(), mid.size());
+    std::memcpy(m.stage.data() + o_key + mid.size(), cid.data(), cid.size());
+    m.in.need(total);
+    m.out.need(TrackLayout(1).total);
+    hip_check(hipMemcpyAsync(m.in.p, m.stage.data(), total, hipMemcpyHostToDevice, m.stream), "H2D");
+    TrackResults r;
+    m.track(m.in.b() + o_key, mid.size() + cid.size(), reinterpret_cast<const uint64_t*>(m.in.p),
+            reinterpret_cast<const uint32_t*>(m.in.b() + o_mlen), reinterpret_cast<const uint64_t*>(m.in.b() + o_cpos),
+            reinterpret_cast<const uint32_t*>(m.in.b() + o_clen), 1, m.out.b(), r);
+    m.settle(d, mid, r, 0, now_ns);
+    return d;
+}
+
+std::vector<Delivery> DeliveryTracker::on_batch(const ParsedBatch& batch, std::uint64_t now_ns) {
+    Impl& m = *impl_;
+    const size_t n = batch.size();
+    std::vector<Delivery> res(n);
+    if (!n) return res;
+    const Descriptors* d = batch.desc_.get();
+    const uint64_t base0 = batch.rec_off_[0], bytes = batch.rec_off_[n] - base0;
+    const char* host = reinterpret_cast<const char*>(batch.data_ + base0);
+    constexpr size_t P = SBE_DLV_PATHS;
+    // staged: rec_off rebased to 0 [n + 1] | status | flags | view_off | view_len | select | the
+    // records | room for the decoded forms of escaped ids (never longer than their tokens)
+    const size_t o_st = al64(8 * (n + 1)), o_fl = o_st + al64(n), o_vo = o_fl + al64(n), o_vl = o_vo + al64(20 * n),
+                 o_sel = o_vl + al64(20 * n), o_data = o_sel + al64(n), total_in = o_data + 2 * bytes + 16;
+    m.stage.resize(o_data + bytes);
+    uint8_t* hp = m.stage.data();
+    uint64_t* ro = reinterpret_cast<uint64_t*>(hp);
+    for (size_t i = 0; i <= n; ++i) ro[i] = batch.rec_off_[i] - base0;
+    for_ranges(n, 1024, [&](size_t x, size_t y) {
+        ParseResult r;
+        for (size_t i = x; i < y; ++i) {
+            hp[o_st + i] = d->status(i);
+            hp[o_fl + i] = d->flags(i);
+            std::memcpy(hp + o_vo + 20 * i, d->off(i), 20);
+            std::memcpy(hp + o_vl + 20 * i, d->len(i), 20);
+            hp[o_sel + i] = 0;
+            if (d->status(i) != SBE_ST_TM) continue;
+            batch.result_into(i, r);
+            hp[o_sel + i] = order_callback_looks(r) ? 1 : 0;
+        }
+    });
+    if (bytes) std::memcpy(hp + o_data, host, bytes);
+    // results: the extract's five arrays | the keys' nine and totals | the table calls' results
+    const TrackLayout L(n);
+    size_t q = 0;
+    const size_t j_doc = q; q = al64(q + n);
+    const size_t j_root = q; q = al64(q + n);
+    const size_t j_kind = q; q = al64(q + P * n);
+    const size_t j_off = q; q = al64(q + 4 * P * n);
+    const size_t j_len = q; q = al64(q + 4 * P * n);
+    const size_t k_mpos = q; q = al64(q + 8 * n);
+    const size_t k_mlen = q; q = al64(q + 4 * n);
+    const size_t k_cpos = q; q = al64(q + 8 * n);
+    const size_t k_clen = q; q = al64(q + 4 * n);
+    const size_t k_ckind = q; q = al64(q + n);
+    const size_t k_opos = q; q = al64(q + 8 * n);
+    const size_t k_olen = q; q = al64(q + 4 * n);
+    const size_t k_okind = q; q = al64(q + n);
+    const size_t k_sel = q; q = al64(q + n);
+    const size_t k_tot = q; q = al64(q + 16);
+    const size_t o_res = q;
+    m.in.need(total_in);
+    m.out.need(o_res + L.total);
+    hip_check(hipMemcpyAsync(m.in.p, hp, o_data + bytes, hipMemcpyHostToDevice, m.stream), "H2D");
+    uint8_t* di = m.in.b();
+    uint8_t* dq = m.out.b();
+    const uint64_t* d_ro = reinterpret_cast<const uint64_t*>(di);
+    const sbe_decoded dec{di + o_st, di + o_fl, nullptr, nullptr, reinterpret_cast<uint32_t*>(di + o_vo),
+                          reinterpret_cast<uint32_t*>(di + o_vl), nullptr};
+    {
+        std::vector<uint8_t> depth, names;
+        std::vector<uint32_t> name_off{0};
+        for (const JsonPath& p : order_id_paths()) {
+            depth.push_back((uint8_t)p.names.size());
+            for (const std::string& nm : p.names) {
+                names.insert(names.end(), nm.begin(), nm.end());
+                name_off.push_back((uint32_t)names.size());
+            }
+        }
+        const sbe_json_paths ps{(uint32_t)depth.size(), depth.data(), names.data(), name_off.data()};
+        sbe_json_out jo{dq + j_doc, dq + j_root, dq + j_kind, reinterpret_cast<uint32_t*>(dq + j_off),
+                        reinterpret_cast<uint32_t*>(dq + j_len)};
+        if (sbe_json_extract_batch(di + o_data, d_ro, n, &dec, 3, di + o_sel, &ps, &jo, nullptr, 0, m.stream) != SBE_OK)
+            fail("sbe_json_extract_batch");
+        const sbe_delivery_key_out ko{reinterpret_cast<uint64_t*>(dq + k_mpos), reinterpret_cast<uint32_t*>(dq + k_mlen),
+                                      reinterpret_cast<uint64_t*>(dq + k_cpos), reinterpret_cast<uint32_t*>(dq + k_clen),
+                                      dq + k_ckind,
+                                      reinterpret_cast<uint64_t*>(dq + k_opos), reinterpret_cast<uint32_t*>(dq + k_olen),
+                                      dq + k_okind, dq + k_sel, reinterpret_cast<uint64_t*>(dq + k_tot)};
+        if (sbe_delivery_keys(d_ro, n, &dec, di + o_sel, &jo, &ko, m.stream) != SBE_OK) fail("sbe_delivery_keys");
+    }
+    std::vector<uint64_t> mpos(n), cpos(n), opos(n);
+    std::vector<uint32_t> mlen(n), clen(n), olen(n);
+    std::vector<uint8_t> ckind(n), okind(n), sel(n);
+    uint64_t totals[2] = {0, 0};
+    auto back = [&](void* dst, size_t off, size_t len) {
+        hip_check(hipMemcpyAsync(dst, dq + off, len, hipMemcpyDeviceToHost, m.stream), "D2H");
+    };
+    back(mpos.data(), k_mpos, 8 * n);
+    back(mlen.data(), k_mlen, 4 * n);
+    back(cpos.data(), k_cpos, 8 * n);
+    back(clen.data(), k_clen, 4 * n);
+    back(ckind.data(), k_ckind, n);
+    back(opos.data(), k_opos, 8 * n);
+    back(olen.data(), k_olen, 4 * n);
+    back(okind.data(), k_okind, n);
+    back(sel.data(), k_sel, n);
+    back(totals, k_tot, 16);
+    m.sync();
+    // the id strings, cut from the caller's bytes; escaped ones decoded, and the decoded client ids
+    // appended behind the staged batch so that the tables compare what decodeString gives
+    std::vector<uint8_t> extra;
+    bool patched = false;
+    for (size_t i = 0; i < n; ++i) {
+        if (!sel[i]) continue;
+        Delivery& r = res[i];
+        r.selected = true;
+        if (clen[i] != SBE_NO_KEY) {
+            const std::string_view tok(host + cpos[i], clen[i]);
+            if (ckind[i] == SBE_JX_STRING_ESC) {
+                r.client_order_id = json_unescape(tok);
+                cpos[i] = bytes + extra.size();
+                clen[i] = (uint32_t)r.client_order_id.size();
+                extra.insert(extra.end(), r.client_order_id.begin(), r.client_order_id.end());
+                patched = true;
+            } else {
+                r.client_order_id.assign(tok);
+            }
+        }
+        if (olen[i] != SBE_NO_KEY) {
+            const std::string_view tok(host + opos[i], olen[i]);
+            r.order_id = okind[i] == SBE_JX_STRING_ESC ? json_unescape(tok) : std::string(tok);
+        }
+    }
+    if (patched) {
+        if (!extra.empty())
+            hip_check(hipMemcpyAsync(di + o_data + bytes, extra.data(), extra.size(), hipMemcpyHostToDevice, m.stream), "H2D");
+        hip_check(hipMemcpyAsync(dq + k_cpos, cpos.data(), 8 * n, hipMemcpyHostToDevice, m.stream), "H2D");
+        hip_check(hipMemcpyAsync(dq + k_clen, clen.data(), 4 * n, hipMemcpyHostToDevice, m.stream), "H2D");
+    }
+    TrackResults tr;
+    m.track(di + o_data, bytes + extra.size(), reinterpret_cast<const uint64_t*>(dq + k_mpos),
+            reinterpret_cast<const uint32_t*>(dq + k_mlen), reinterpret_cast<const uint64_t*>(dq + k_cpos),
+            reinterpret_cast<const uint32_t*>(dq + k_clen), n, dq + o_res, tr);
+    bool long_ids = false;
+    for (size_t i = 0; i < n; ++i) {
+        if (!sel[i]) continue;
+        const std::string_view mid = mlen[i] == SBE_NO_KEY ? std::string_view() : std::string_view(host + mpos[i], mlen[i]);
+        m.settle(res[i], mid, tr, i, now_ns);
+        long_ids |= mid.size() > SBE_INFLIGHT_KEY_MAX;
+    }
+    if (long_ids)  // as for the table's ids: the count recorded after the whole batch
+        for (size_t i = 0; i < n; ++i)
+            if (sel[i] && mlen[i] != SBE_NO_KEY && mlen[i] > SBE_INFLIGHT_KEY_MAX && res[i].already_processed)
+                res[i].redeliveries = (uint32_t)(m.long_msgs[std::string(host + mpos[i], mlen[i])] - 1);
+    return res;
 }
 
 std::vector<CommitOffset> CommitManager::parse_commit_offsets_batch(const std::vector<std::string>& payloads,

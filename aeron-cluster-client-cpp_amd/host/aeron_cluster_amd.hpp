@@ -391,6 +391,7 @@ public:
 private:
     friend class MessageParser;
     friend class AutoCommitter;
+    friend class DeliveryTracker;
     std::shared_ptr<const detail::Descriptors> desc_;  // host copy of the device descriptors
     const std::uint8_t* data_ = nullptr;               // the caller's records (borrowed)
     const std::uint64_t* rec_off_ = nullptr;           // the caller's offsets (borrowed)
@@ -533,6 +534,62 @@ public:
     // entries that can still match (reads the table's header back), table capacity, rehashes so far
     std::size_t size() const;
     std::uint64_t capacity() const;
+    std::uint64_t rehashes() const;
+
+private:
+    struct Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// What the subscriber's callback of examples/pubsub_reconnect_test.cpp (:576-716) finds out about
+// one delivered record.
+struct Delivery {
+    bool selected = false;            // the callback's outer if (:578) holds; false: nothing else is set
+    bool already_processed = false;   // message_id was in received_message_ids (:625-635)
+    std::uint32_t redeliveries = 0;   // batch form: the id's redeliveries recorded after the whole batch, i.e. what
+                                      // record_duplicate_delivery (:83-90) returned for its last redelivery in it
+    std::string client_order_id, order_id;  // extract_order_ids of the record
+    bool duplicate_client_order = false;    // a first delivery whose client_order_id was received before (:653-661)
+    bool was_sent = false;                  // client_order_id is in sent_client_order_ids (:674)
+    bool latency_recorded = false;          // the first delivery that finds a send time (:680-691)
+    std::int64_t latency_ns = 0;            // now_ns - send time, when latency_recorded
+};
+
+// The tables that callback keeps across calls, on the device: received_message_ids with the
+// per-id counts of duplicate_delivery_counts, received_client_order_ids, and the publisher's
+// sent_client_order_ids / client_order_send_time (:455-459, :498-501), three sbe_inflight_* tables
+// driven by sbe_inflight_note_keys / sbe_inflight_lookup_keys.  on_batch stages the batch once and
+// runs extract (the nine order-id paths), sbe_delivery_keys, note (message ids), note (client
+// ids) and lookup (sent) back to back on one stream; per-record codes come back, the id strings
+// are cut from the caller's bytes.  Ids over SBE_INFLIGHT_KEY_MAX bytes live in host sets, ids
+// spelled with escapes are decoded on the host and appended behind the staged batch before the
+// table calls, so "ab\u0063" is abc.  Tables are rehashed before a batch that would take their
+// used slots past half the capacity.  A batch takes one clock reading (now_ns), as
+// AckCorrelator::on_egress_batch does.  Differences from the example, both in note_sent: a
+// client_order_id sent twice keeps its first send time (the example overwrites it), and ids are
+// expected to be noted as sent before their deliveries arrive (the publisher does, :455-501).
+// One thread at a time.
+class DeliveryTracker {
+public:
+    explicit DeliveryTracker(std::uint64_t initial_capacity = 1u << 16, std::uint32_t tag_bits = 0);
+    ~DeliveryTracker();
+    DeliveryTracker(const DeliveryTracker&) = delete;
+    DeliveryTracker& operator=(const DeliveryTracker&) = delete;
+
+    // the publisher's two inserts for every id
+    void note_sent(const std::vector<std::string>& client_order_ids, std::uint64_t ts_ns);
+    // the callback for every record of the batch, in order
+    std::vector<Delivery> on_batch(const ParsedBatch& batch, std::uint64_t now_ns);
+    // the one-record form: a one-record batch of keys (two launches per table, tens of microseconds)
+    Delivery on_message(const ParseResult& result, std::uint64_t now_ns);
+    std::uint64_t messages_received() const;  // records that were not already processed (:636-638)
+    // printMessageComparison (:130-190) as counts: ids sent, ids received, sent and never answered
+    // by a delivery, received and never sent
+    std::size_t sent() const;
+    std::size_t received() const;
+    std::size_t missing() const;
+    std::size_t extra() const;
+    void clear_duplicate_tracking();  // :70-73: the redelivery counts start again
     std::uint64_t rehashes() const;
 
 private:

@@ -137,6 +137,11 @@ class _JsonOut(ctypes.Structure):
                 ("off", ctypes.c_void_p), ("len", ctypes.c_void_p)]
 
 
+class _DeliveryKeyOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("msg_pos", "msg_len", "coid_pos", "coid_len", "coid_kind", "oid_pos",
+                                               "oid_len", "oid_kind", "selected", "totals")]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise SbeError(f"{LIB_PATH} is missing: build it with `make -C aeron-cluster-client-cpp_amd` "
@@ -245,6 +250,17 @@ def _load():
                                             ctypes.c_size_t, ctypes.c_void_p]
     lib.sbe_inflight_rehash.restype = ctypes.c_int
     lib.sbe_inflight_rehash.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    for name in ("sbe_inflight_note_keys", "sbe_inflight_lookup_keys"):
+        f = getattr(lib, name)
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                      ctypes.c_size_t, ctypes.c_void_p]
+    lib.sbe_inflight_reset_values.restype = ctypes.c_int
+    lib.sbe_inflight_reset_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.sbe_delivery_keys.restype = ctypes.c_int
+    lib.sbe_delivery_keys.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_Decoded), ctypes.c_void_p,
+                                      ctypes.POINTER(_JsonOut), ctypes.POINTER(_DeliveryKeyOut), ctypes.c_void_p]
     lib.sbe_profile_enable.restype = ctypes.c_int
     lib.sbe_order_json_workspace_size.argtypes = [ctypes.c_uint64]
     lib.sbe_order_json_workspace_size.restype = ctypes.c_size_t
@@ -909,6 +925,10 @@ def emit_commit_offsets(data, rec_off, dec: Decoded, plan: CommitPlan, topic_ids
 INF_INSERTED, INF_DUPLICATE, INF_SKIPPED, INF_KEY_TOO_LONG, INF_FULL = range(5)
 ACK_NONE, ACK_MATCHED, ACK_UNMATCHED, ACK_LONG_ID = range(4)
 INFLIGHT_KEY_MAX = 40
+# sbe_inflight_note_keys / sbe_inflight_lookup_keys: delivery tracking
+DLV_NONE, DLV_NEW, DLV_AGAIN, DLV_LONG, DLV_FULL = range(5)
+SENT_NONE, SENT_UNKNOWN, SENT_FIRST, SENT_REPEAT, SENT_LONG = range(5)
+NO_KEY = 0xFFFFFFFF
 
 
 @dataclass
@@ -921,6 +941,83 @@ class AckMatches:
         import numpy as np
         return {"code": self.code.cpu().numpy(), "base_ns": self.base_ns.cpu().numpy().view(np.uint64),
                 "counts": self.counts.cpu().numpy().view(np.uint64)}
+
+
+@dataclass
+class KeyNotes:
+    code: torch.Tensor    # uint8 [n]  DLV_*
+    count: torch.Tensor   # int32 [n]  (u32) redeliveries of the key recorded after the call
+    totals: torch.Tensor  # int64 [2]  (u64) NEW, AGAIN
+
+    def numpy(self):
+        import numpy as np
+        return {"code": self.code.cpu().numpy(), "count": self.count.cpu().numpy().view(np.uint32),
+                "totals": self.totals.cpu().numpy().view(np.uint64)}
+
+
+@dataclass
+class KeyLookups:
+    code: torch.Tensor    # uint8 [n]  SENT_*
+    value: torch.Tensor   # int64 [n]  (u64) the stored value (SENT_FIRST), else 0
+    totals: torch.Tensor  # int64 [3]  (u64) FIRST, REPEAT, UNKNOWN + LONG
+
+    def numpy(self):
+        import numpy as np
+        return {"code": self.code.cpu().numpy(), "value": self.value.cpu().numpy().view(np.uint64),
+                "totals": self.totals.cpu().numpy().view(np.uint64)}
+
+
+_DELIVERY_KEYS = (("msg_pos", "int64"), ("msg_len", "int32"), ("coid_pos", "int64"), ("coid_len", "int32"),
+                  ("coid_kind", "uint8"), ("oid_pos", "int64"), ("oid_len", "int32"), ("oid_kind", "uint8"),
+                  ("selected", "uint8"), ("totals", "int64"))
+
+
+@dataclass
+class DeliveryKeys:
+    msg_pos: torch.Tensor    # int64 [n]  (u64) message_id: a position in the batch buffer
+    msg_len: torch.Tensor    # int32 [n]  (u32) NO_KEY: not selected, or an empty id
+    coid_pos: torch.Tensor   # int64 [n]  client_order_id
+    coid_len: torch.Tensor   # int32 [n]
+    coid_kind: torch.Tensor  # uint8 [n]  JX_STRING, JX_STRING_ESC (raw range: decode before comparing) or JX_MISSING
+    oid_pos: torch.Tensor    # int64 [n]  order_id
+    oid_len: torch.Tensor    # int32 [n]
+    oid_kind: torch.Tensor   # uint8 [n]
+    selected: torch.Tensor   # uint8 [n]  the callback's outer if holds
+    totals: torch.Tensor     # int64 [2]  selected records, ids of kind JX_STRING_ESC
+
+    def numpy(self):
+        import numpy as np
+        u = {"int64": np.uint64, "int32": np.uint32, "uint8": np.uint8}
+        return {k: getattr(self, k).cpu().numpy().view(u[t]) for k, t in _DELIVERY_KEYS}
+
+
+def delivery_keys(rec_off, dec: Decoded, ids: JsonFields, select=None, out: DeliveryKeys | None = None,
+                  stream=None) -> DeliveryKeys:
+    """The three keys the subscriber's callback looks up per record
+    (examples/pubsub_reconnect_test.cpp:592-691) as ranges of the batch buffer: message_id, and the
+    client_order_id / order_id picked from `ids`, an extract_json(..., ORDER_ID_PATHS) of the same
+    batch.  select: optional uint8 [n], the callback's outer condition.  Feed msg_* and coid_* to
+    Inflight.note_keys and coid_* to Inflight.lookup_keys with the batch buffer as buf."""
+    rec_off = _dev(rec_off, torch.int64, "rec_off")
+    select = _dev(select, torch.uint8, "select")
+    n = int(rec_off.numel()) - 1
+    dev = rec_off.device
+    if ids.kind.dim() != 2 or ids.kind.shape[1] != len(ORDER_ID_PATHS):
+        raise SbeError("delivery_keys: ids must come from an extract over ORDER_ID_PATHS")
+    if min(ids.doc.numel(), ids.kind.shape[0]) < n or (select is not None and select.numel() < n):
+        raise SbeError("delivery_keys: ids or select hold fewer than n records")
+    if out is None:
+        out = DeliveryKeys(*(torch.empty(2 if k == "totals" else max(n, 1), dtype=getattr(torch, t), device=dev)
+                             for k, t in _DELIVERY_KEYS))
+    d = _Decoded(*(getattr(dec, f).data_ptr() for f in ("status", "flags", "hdr", "ts", "view_off", "view_len")))
+    j = _JsonOut(*(getattr(ids, f).data_ptr() for f, _ in _JSON_KEYS))
+    o = _DeliveryKeyOut(*(getattr(out, k).data_ptr() for k, _ in _DELIVERY_KEYS))
+    rc = lib().sbe_delivery_keys(_ptr(rec_off), n, ctypes.byref(d), _ptr(select), ctypes.byref(j), ctypes.byref(o),
+                                 _stream(stream))
+    _check(rc, "sbe_delivery_keys")
+    if n < out.selected.numel():
+        out = DeliveryKeys(*(getattr(out, k) if k == "totals" else getattr(out, k)[:n] for k, _ in _DELIVERY_KEYS))
+    return out
 
 
 class Inflight:
@@ -1010,6 +1107,58 @@ class Inflight:
         """{capacity, live, used} read back from the table's header (synchronises)."""
         h = self.table[:24].cpu().numpy().view("<u8")
         return {"capacity": int(h[0]), "live": int(h[1]), "used": int(h[2])}
+
+    def stats_ex(self) -> dict:
+        """stats() and `answered`: the live entries a lookup_keys call has answered (synchronises)."""
+        h = self.table[:40].cpu().numpy().view("<u8")
+        return {"capacity": int(h[0]), "live": int(h[1]), "used": int(h[2]), "answered": int(h[4])}
+
+    def _keys_call(self, fn, name, buf, key_pos, key_len, result_dtype, n_totals, n, buf_bytes, code, result, totals,
+                   workspace, stream):
+        buf = _dev(buf, torch.uint8, "buf")
+        key_pos = _dev(key_pos, torch.int64, "key_pos")
+        key_len = _dev(key_len, torch.int32, "key_len")
+        if n is None:
+            n = int(key_len.numel())
+        if buf_bytes is None:
+            buf_bytes = int(buf.numel())
+        if buf_bytes > buf.numel():
+            raise SbeError(f"{name}: buf_bytes exceeds the buffer")
+        if buf.numel() == 0:
+            buf = torch.zeros(16, dtype=torch.uint8, device=self.device)
+        if code is None:
+            code = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        if result is None:
+            result = torch.empty(max(n, 1), dtype=result_dtype, device=self.device)
+        if totals is None:
+            totals = torch.empty(n_totals, dtype=torch.int64, device=self.device)
+        ws = self._workspace(n, workspace)
+        rc = fn(_ptr(self.table), _ptr(buf), int(buf_bytes), _ptr(key_pos), _ptr(key_len), n, _ptr(code), _ptr(result),
+                _ptr(totals), _ptr(ws), int(ws.numel()), _stream(stream))
+        _check(rc, name)
+        return code[:n], result[:n], totals[:n_totals]
+
+    def note_keys(self, buf, key_pos, key_len, n=None, buf_bytes=None, code=None, count=None, totals=None,
+                  workspace=None, stream=None) -> KeyNotes:
+        """Test-and-insert that counts, for n records in order: key i = buf[key_pos[i]:][:key_len[i]]
+        (key_pos int64 holding u64, key_len int32 holding u32, NO_KEY: none), clamped into buf_bytes
+        (default: all of buf).  The received_message_ids / received_client_order_ids bookkeeping of
+        examples/pubsub_reconnect_test.cpp:625-667: code (DLV_*), count (the key's deliveries after
+        the call, minus one) and totals {NEW, AGAIN}."""
+        return KeyNotes(*self._keys_call(lib().sbe_inflight_note_keys, "sbe_inflight_note_keys", buf, key_pos, key_len,
+                                         torch.int32, 2, n, buf_bytes, code, count, totals, workspace, stream))
+
+    def lookup_keys(self, buf, key_pos, key_len, n=None, buf_bytes=None, code=None, value=None, totals=None,
+                    workspace=None, stream=None) -> KeyLookups:
+        """Lookup with mark-on-first against the keys remember() stored (:669-691): code (SENT_*),
+        value (the stored time for SENT_FIRST, else 0) and totals {FIRST, REPEAT, UNKNOWN + LONG}."""
+        return KeyLookups(*self._keys_call(lib().sbe_inflight_lookup_keys, "sbe_inflight_lookup_keys", buf, key_pos,
+                                           key_len, torch.int64, 3, n, buf_bytes, code, value, totals, workspace,
+                                           stream))
+
+    def reset_values(self, stream=None):
+        """clear_duplicate_tracking (:70-73): every live entry back to one delivery, its count to 0."""
+        _check(lib().sbe_inflight_reset_values(_ptr(self.table), _stream(stream)), "sbe_inflight_reset_values")
 
     def rehash(self, capacity: int, stream=None, tag_bits=None) -> "Inflight":
         """A new table of `capacity` slots holding this one's live entries (erased slots reclaimed)."""

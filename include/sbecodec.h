@@ -72,6 +72,16 @@
  *                                  ack callback wired at :1648: find / erase in inflight_ and the time
  *                                  the round trip is measured from (sbe_inflight_init, _rehash,
  *                                  _table_size, _workspace_size manage the device table)
+ * sbe_inflight_note_keys()        the received_message_ids / received_client_order_ids bookkeeping of the
+ *                                  subscriber's callback, examples/pubsub_reconnect_test.cpp:625-667
+ *                                  (again from :1190): insert-if-new, already_processed and the
+ *                                  per-id count of record_duplicate_delivery (:83-90)
+ * sbe_inflight_lookup_keys()      the correlation with the publisher, :669-691: was_sent and the
+ *                                  latency recorded once per client_order_id, against the ids
+ *                                  sbe_inflight_remember stored (:455-459, :498-501)
+ *                                  (sbe_inflight_reset_values: clear_duplicate_tracking, :70-73)
+ * sbe_delivery_keys()             the three keys of those lookups per record: message_id and the
+ *                                  client_order_id / order_id the callback picks, :592-619
  * sbe_json_extract_batch()        what a consumer's callback reads out of result.payload: the
  *                                  Json::parseFromStream + isMember / operator[] lookups of
  *                                  examples/pubsub_reconnect_test.cpp:576-620 (again :1142-1160) and of
@@ -632,6 +642,7 @@ int sbe_emit_commit_offsets_ex(const uint8_t* in, const uint64_t* rec_off, uint6
  * caller that reads them with its own copy:
  *   +0 u64 capacity   +8 u64 live (entries that can still match)
  *   +16 u64 used (slots that are not empty, erased ones included)   +24 u32 tag_bits
+ *   +32 u64 answered (live entries a sbe_inflight_lookup_keys call has answered)
  * Limits: keys are stored inline, zero-padded, up to SBE_INFLIGHT_KEY_MAX bytes (the reference's
  * "pub_" + now_nanos() is at most 24); a longer key is reported, not stored (the host mirror keeps
  * those in a map of its own).  Erased slots are not reused by inserts: sbe_inflight_rehash into a
@@ -664,7 +675,8 @@ size_t sbe_inflight_table_size(uint64_t capacity);
  * SBE_EINVAL: null or misaligned table, bad capacity, table_bytes too small, tag_bits > 30. */
 int sbe_inflight_init(void* table, size_t table_bytes, uint64_t capacity, uint32_t tag_bits, void* stream);
 
-/* Workspace bytes of sbe_inflight_remember and sbe_inflight_match_acks for n records (4-B aligned). */
+/* Workspace bytes of sbe_inflight_remember, sbe_inflight_match_acks, sbe_inflight_note_keys and
+ * sbe_inflight_lookup_keys for n records (4-B aligned). */
 size_t sbe_inflight_workspace_size(uint64_t n);
 
 /* remember_outgoing for records 0 .. n-1, in order.  Key i is arena[key_off[i*stride] ..) with
@@ -710,6 +722,106 @@ int sbe_inflight_match_acks(void* table, const uint8_t* in, const uint64_t* rec_
  * that find no slot are dropped).  src is unchanged; used(dst) == live(src) afterwards.  One launch
  * on `stream`.  SBE_EINVAL: null, misaligned or identical tables. */
 int sbe_inflight_rehash(const void* src, void* dst, void* stream);
+
+/* ================================ delivery tracking ================================ */
+/* What the subscriber's callback keeps per delivered record
+ * (examples/pubsub_reconnect_test.cpp:625-691, the same code again from :1190), on the tables of
+ * the section above: which message ids and client order ids were seen before and how often, and
+ * which sent order a delivery answers.  The example's sets are never evicted, so the results are
+ * exactly those of the sequential callback.
+ *
+ * Keys are byte ranges anywhere in one device buffer: key i is buf[key_pos[i] .. key_pos[i] +
+ * key_len[i]) (key_pos: device u64 [n], 8-B aligned; key_len: device u32 [n], 4-B aligned;
+ * SBE_NO_KEY: the record has no key).  A range is clamped into [0, buf_bytes) before a byte of it
+ * is read: key_pos to at most buf_bytes, then key_len to what is left (so a key_pos at or past
+ * buf_bytes is the empty key).  A zero-length key is a key, as for sbe_inflight_remember.
+ * sbe_inflight_workspace_size(n) also sizes the workspace of both calls.  Each result depends on
+ * the table before the call and on the record order only. */
+#define SBE_NO_KEY 0xFFFFFFFFu
+/* code[i] of sbe_inflight_note_keys */
+#define SBE_DLV_NONE 0u  /* no key: nothing is looked up */
+#define SBE_DLV_NEW 1u   /* the key was not live and no smaller index of this call has it: it is stored */
+#define SBE_DLV_AGAIN 2u /* the key was live, or a smaller index of this call has it */
+#define SBE_DLV_LONG 3u  /* over SBE_INFLIGHT_KEY_MAX bytes (after the clamp): not stored */
+#define SBE_DLV_FULL 4u  /* no free slot was found */
+/* code[i] of sbe_inflight_lookup_keys */
+#define SBE_SENT_NONE 0u    /* no key */
+#define SBE_SENT_UNKNOWN 1u /* the key is not live */
+#define SBE_SENT_FIRST 2u   /* live, not yet answered, and the smallest index of the call that has it:
+                               value[i] is the stored value; the entry becomes answered and stays live */
+#define SBE_SENT_REPEAT 3u  /* live, and answered before the call or a smaller index of the call has it */
+#define SBE_SENT_LONG 4u    /* over SBE_INFLIGHT_KEY_MAX bytes: it cannot be in the table */
+
+/* Test-and-insert that counts.  The 8-byte value of a slot holds the number of deliveries of its
+ * key: every record that is NEW or AGAIN adds one (a key stored by sbe_inflight_remember counts on
+ * from its send time).  code: [n] u8 SBE_DLV_*.  count: [n] u32, for NEW and AGAIN the low 32 bits
+ * of (the key's value after the whole call) - 1, i.e. what record_duplicate_delivery returned for
+ * the last redelivery of that id in the call; 0 for every other code.  totals: NULL or device
+ * u64 [2] {NEW, AGAIN}, zeroed by the call (8-B aligned).  With used + the distinct new keys of the
+ * call below capacity no record is SBE_DLV_FULL.  header +8 live and +16 used grow by the NEW
+ * records.  A memset of totals and two launches on `stream`.  SBE_EINVAL (before any launch): a
+ * null table / buf / key_pos / key_len / code / count / workspace, n >= 2^32, table not 64-B,
+ * key_pos / totals not 8-B, key_len / count / workspace not 4-B aligned; SBE_ENOSPC: workspace too
+ * small.  n == 0 is SBE_OK with totals zeroed: only table and totals are looked at. */
+int sbe_inflight_note_keys(void* table, const uint8_t* buf, uint64_t buf_bytes, const uint64_t* key_pos,
+                           const uint32_t* key_len, uint64_t n, uint8_t* code, uint32_t* count, uint64_t* totals,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* Lookup that marks on first sight.  "Answered" is state of a live entry (bit 0 of its slot word;
+ * header +32 u64 answered counts such entries): sbe_inflight_remember still reports the key as
+ * SBE_INF_DUPLICATE and leaves it answered, sbe_inflight_match_acks still matches and erases it
+ * (answered drops), sbe_inflight_rehash carries it over.  code: [n] u8 SBE_SENT_*.  value: [n] u64,
+ * the stored value for FIRST, 0 otherwise (8-B aligned).  totals: NULL or device u64 [3]
+ * {FIRST, REPEAT, UNKNOWN + LONG}, zeroed by the call.  Launches, errors and n == 0 as for
+ * sbe_inflight_note_keys (value in the place of count). */
+int sbe_inflight_lookup_keys(void* table, const uint8_t* buf, uint64_t buf_bytes, const uint64_t* key_pos,
+                             const uint32_t* key_len, uint64_t n, uint8_t* code, uint64_t* value, uint64_t* totals,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* clear_duplicate_tracking (:70-73) for a table of sbe_inflight_note_keys: the value of every live
+ * entry goes back to 1, one delivery and no redelivery, so every count is 0 again and the next
+ * redelivery of an id reports 1, as record_duplicate_delivery does after the example cleared its
+ * counters (a value of 0 would leave every id seen before the call one short for ever after).
+ * Membership and the answered state stay.  One launch.  SBE_EINVAL: null or misaligned table. */
+int sbe_inflight_reset_values(void* table, void* stream);
+
+/* The paths sbe_delivery_keys expects `ids` to have been extracted over (view 3), in this order:
+ *   0 message                         1 message.message
+ *   2 message.message.client_order_id 3 message.message.order_id
+ *   4 message.message.order_details   5 message.message.order_details.client_order_id
+ *   6 message.order_details           7 message.order_details.client_order_id
+ *   8 uuid */
+#define SBE_DLV_PATHS 9u
+
+typedef struct sbe_delivery_key_out { /* device arrays of n elements; u64 8-B, u32 4-B aligned */
+    uint64_t* msg_pos;  /* rec_off[i] + view 2 (message_id), clamped into the record */
+    uint32_t* msg_len;  /* SBE_NO_KEY: not selected, or an empty id (:628) */
+    uint64_t* coid_pos; /* the client_order_id: rec_off[i] + the member's range, clamped into the record */
+    uint32_t* coid_len; /* SBE_NO_KEY: no string was found, or an empty one (:648, :669) */
+    uint8_t* coid_kind; /* SBE_JX_STRING, SBE_JX_STRING_ESC (the raw range: the host decodes it before
+                           it can be compared) or SBE_JX_MISSING */
+    uint64_t* oid_pos;  /* the order_id, likewise */
+    uint32_t* oid_len;
+    uint8_t* oid_kind;
+    uint8_t* selected;  /* 1: the callback's outer if (:578) holds: SBE_ST_TM and select[i] */
+    uint64_t* totals;   /* [2] {selected records, ids of kind SBE_JX_STRING_ESC}, zeroed by the call */
+} sbe_delivery_key_out;
+
+/* The keys of a decoded batch: dec is a parse-mode decode of rec_off's records, ids an
+ * sbe_json_extract_batch(view 3) of them over the SBE_DLV_PATHS paths, select NULL (every
+ * TopicMessage) or a device u8 [n].  Positions are offsets into the buffer rec_off indexes, ready
+ * for the two calls above.  The ids follow the callback (:592-619): the document must be
+ * SBE_JX_OK and its root an object; message.message an object: client = string 2, order =
+ * string 3, and an empty client falls through to string 5 when 4 is an object; otherwise
+ * message.order_details (6) an object: client = string 7; an empty order is replaced by a
+ * non-empty string 8.  Only strings count.  A non-empty SBE_JX_STRING_ESC decodes to a non-empty
+ * string and stops a fall-through.  The kind is that of the member the rule ended on (an empty
+ * string keeps SBE_JX_STRING with length SBE_NO_KEY); a position whose length is SBE_NO_KEY is
+ * rec_off[i].  One launch after a memset of totals; every element i < n of the nine arrays is
+ * written.  n == 0 is SBE_OK with totals zeroed.  SBE_EINVAL: a null pointer (select excepted),
+ * n >= 2^32, an array below its alignment. */
+int sbe_delivery_keys(const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec, const uint8_t* select,
+                      const sbe_json_out* ids, const sbe_delivery_key_out* out, void* stream);
 
 /* ============================ Aeron fragment reassembly ============================ */
 /* Replaces LocalFragmentReassembler::onFragment (src/cluster_client.cpp:39-82) for a batch of

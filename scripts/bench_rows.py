@@ -26,6 +26,11 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
                          acks (about 10 % unknown ids, 1 % repeated ids) decoded on-egress and matched;
                          remember, match and the decode of the same ack batch timed in the same run, and
                          a one-thread std::unordered_map doing the same sequence on the host
+  delivery_track         1 M decoded fixed-256 Orders with nested payloads, about 10 % of them redeliveries,
+                         against 2 M-slot tables and 1 M sent client order ids: sbe_delivery_keys, note
+                         (message ids), note (client ids) and lookup (sent) timed as one region, the
+                         nine-path extract before it timed beside it, and a one-thread std::set /
+                         std::map run of the example's callback on the host
 Rows whose buffers fit the 256 MB MALL a few times over rotate over --rotate (3) copies of their
 inputs and outputs (step k uses copy k mod R), as bench.py does, so no step finds its inputs in the
 cache a previous step left them in; config 4's 16.8 M-record batch (~6.5 GB) needs no rotation.
@@ -786,11 +791,114 @@ def row_ack_correlate(steps, warmup):
     line("ack_correlate", n, (ms_rem + ms_match) * 1e-3, kernels)
 
 
+def row_delivery_track(steps, warmup):
+    """The second half of the subscriber's callback (examples/pubsub_reconnect_test.cpp:625-691) for
+    1 M decoded fixed-256 Orders whose payloads carry message.message.client_order_id / order_id;
+    about 10 % of the records repeat an earlier record of the batch.  Every step starts from empty
+    message-id and client-id tables and a sent table refilled with the 1 M client ids (not timed).
+    Timed as one region: sbe_delivery_keys + sbe_inflight_note_keys twice + sbe_inflight_lookup_keys
+    (7 launches, 3 memsets); beside it the sbe_json_extract_batch the keys are made from.  Bytes, per
+    record: keys reads 2 + 18 descriptor bytes and 2 + 9 * 9 of the extract and writes 40; each
+    table pass reads a position, a length and the key (12 + 29 or 21), writes its results and the
+    workspace word twice (5 or 9, 8) and touches one 64-B slot twice.  The slot accesses are random
+    64-B lines, as in ack_correlate.  CPU: tests/delivery/set_baseline, one thread."""
+    import subprocess
+    n, cap = 1_000_000, 1 << 21
+    arena, L, ts = T.fixed256_orders(n)
+    rows = arena.reshape(n, 222).copy()
+    shell = b'{"message":{"message":{"client_order_id":"cid_#################","order_id":"oid_#################"}}}'
+    assert len(shell) <= 143
+    pay = np.tile(np.frombuffer(shell.ljust(143), np.uint8), (n, 1))
+    hol = [i for i, c in enumerate(shell) if c == ord("#")]
+    cid_digits = rows[:, 47:190][:, [i for i, c in enumerate(T._PAYLOAD_T) if c == ord("#")][20:]]
+    pay[:, hol[:17]] = cid_digits
+    pay[:, hol[17:]] = cid_digits
+    rows[:, 47:190] = pay
+    sent_keys = np.ascontiguousarray(rows[:, 47 + hol[0] - 4: 47 + hol[0] + 17]).reshape(-1)  # "cid_" + 17 digits
+    rng = np.random.default_rng(0x5EED0F9)
+    again = np.nonzero(rng.random(n) < 0.10)[0]
+    again = again[again > 0]
+    src = (again * rng.random(again.size)).astype(np.int64)
+    for i, j in zip(again.tolist(), src.tolist()):  # in order: a copy of a copy carries the first one's ids
+        rows[i] = rows[j]
+    data, off = T.oracle_encode(rows.reshape(-1), L, ts)[:2]
+    paths = sbecodec.json_path_table(sbecodec.ORDER_ID_PATHS)
+    d0, o0 = dev(data, torch.uint8), dev(np.asarray(off, np.uint64), torch.int64)
+    k0 = dev(sent_keys, torch.uint8)
+    ko0, kl0 = dev((21 * np.arange(n)).astype(np.int32), torch.int32), dev(np.full(n, 21, np.int32), torch.int32)
+
+    def make(k):
+        d, o = d0.clone(), o0.clone()
+        dec = sbecodec.decode_batch(d, o, sbecodec.DEC_PARSE_MESSAGE, out=sbecodec.alloc_decoded(n, "cuda"), in_bytes=data.size)
+        ids = sbecodec.extract_json(d, o, dec, paths)
+        keys = sbecodec.delivery_keys(o, dec, ids)
+        tabs = [sbecodec.Inflight(cap, "cuda") for _ in range(3)]
+        tabs[2].remember(k0, ko0, kl0, ts_default=1000)
+        res = (tabs[0].note_keys(d, keys.msg_pos, keys.msg_len), tabs[1].note_keys(d, keys.coid_pos, keys.coid_len),
+               tabs[2].lookup_keys(d, keys.coid_pos, keys.coid_len))
+        return d, o, dec, ids, keys, tabs, res
+    R = Rot(make)
+    torch.cuda.synchronize()
+    keys0, res0 = R.sets[0][4].numpy(), [r.numpy() for r in R.sets[0][6]]
+    # the model: a record is a redelivery exactly when it is a copy, and client ids are distinct
+    assert np.unique(sent_keys.view("S21")).size == n
+    is_again = np.zeros(n, bool)
+    is_again[again] = True
+    assert list(keys0["totals"]) == [n, 0] and (keys0["msg_len"] == 29).all() and (keys0["coid_len"] == 21).all()
+    assert np.array_equal(res0[0]["code"] == sbecodec.DLV_AGAIN, is_again) and list(res0[0]["totals"]) == [n - again.size, again.size]
+    assert np.array_equal(res0[1]["code"], res0[0]["code"])
+    assert np.array_equal(res0[2]["code"] == sbecodec.SENT_REPEAT, is_again) and list(res0[2]["totals"]) == [n - again.size, again.size, 0]
+    assert (res0[2]["value"][~is_again] == 1000).all()
+
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(steps)]
+
+    def step(e):
+        d, o, dec, ids, keys, tabs, res = R.next()
+        for t in tabs:
+            t.clear()
+        tabs[2].remember(k0, ko0, kl0, ts_default=1000)
+        if e:
+            e[0].record()
+        sbecodec.extract_json(d, o, dec, paths, out=ids)
+        if e:
+            e[1].record()
+        sbecodec.delivery_keys(o, dec, ids, out=keys)
+        if e:
+            e[2].record()
+        tabs[0].note_keys(d, keys.msg_pos, keys.msg_len, code=res[0].code, count=res[0].count, totals=res[0].totals)
+        tabs[1].note_keys(d, keys.coid_pos, keys.coid_len, code=res[1].code, count=res[1].count, totals=res[1].totals)
+        tabs[2].lookup_keys(d, keys.coid_pos, keys.coid_len, code=res[2].code, value=res[2].value, totals=res[2].totals)
+        if e:
+            e[3].record()
+    for _ in range(warmup):
+        step(None)
+    torch.cuda.synchronize()
+    for e in ev:
+        step(e)
+    torch.cuda.synchronize()
+    t = np.array([[e[j].elapsed_time(e[j + 1]) for j in range(3)] for e in ev])
+    ms_ext, ms_keys, ms_tab = (float(v) for v in np.median(t, axis=0))
+    pbytes = 143 * n
+    kernels = {"sbe_delivery_keys (memset + 1 launch)": (ms_keys, (8 + 2 + 16 + 2 + 9 * 9 + 40) * n),
+               "note, note, lookup (3 memsets + 6 launches)": (ms_tab, (2 * (12 + 29 + 5 + 8) + (12 + 21) * 2 + 5 + 9 + 16 + 6 * 64) * n),
+               "sbe_json_extract_batch (9 order-id paths, same run)": (ms_ext, pbytes + (18 + 2 + 9 * 9) * n)}
+    extra = {"row": "delivery_track", "redeliveries": int(again.size), "capacity": cap,
+             "ms_min": {"extract": float(t[:, 0].min()), "keys": float(t[:, 1].min()), "tables": float(t[:, 2].min())},
+             "track_over_extract": (ms_keys + ms_tab) / ms_ext}
+    if not NO_CPU:
+        d = os.path.join(ROOT, "tests", "delivery")
+        subprocess.run(["make", "-s", "-C", d, "set_baseline"], check=True)
+        extra["cpu_set_map_one_thread"] = json.loads(subprocess.run([os.path.join(d, "set_baseline"), str(n)], check=True,
+                                                                    capture_output=True, text=True).stdout)
+    print(json.dumps(extra), flush=True)
+    line("delivery_track", n, (ms_keys + ms_tab) * 1e-3, kernels)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,commit_emit,commit_fallback,ack_correlate")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,commit_emit,commit_fallback,ack_correlate,delivery_track")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -827,6 +935,8 @@ def main():
             row_commit_fallback(args.steps, args.warmup)
         elif r == "ack_correlate":
             row_ack_correlate(args.steps, args.warmup)
+        elif r == "delivery_track":
+            row_delivery_track(args.steps, args.warmup)
         elif r.startswith("lite"):
             row_lite(int(r[4:]), args.steps, args.warmup)
         torch.cuda.empty_cache()
