@@ -4362,6 +4362,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 #include "commit_fallback.hpp"
 #include "json_paths.hpp"
 #include "delivery_keys.hpp"
+#include "delivery_report.hpp"
 
 }  // namespace
 
@@ -5260,6 +5261,121 @@ int sbe_delivery_keys(const uint64_t* rec_off, uint64_t n, const sbe_decoded* de
              ids->root_kind, ids->kind,  ids->off,      ids->len,      out->msg_pos,   out->msg_len,  out->coid_pos,
              out->coid_len, out->coid_kind, out->oid_pos, out->oid_len, out->oid_kind, out->selected, out->totals};
     hipLaunchKernelGGL(sbe_delivery_keys_kernel, dim3((uint32_t)((n + kDkBlk - 1) / kDkBlk)), dim3(kDkBlk), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+size_t sbe_inflight_list_workspace_size(uint32_t limit) {
+    // pass counts, list lengths and `limit` candidates per workgroup, each piece on 16 bytes
+    return limit <= SBE_LIST_MAX ? (size_t)kDrListBlocks * (12 + sizeof(DrCand) * limit) + 64 : 0;
+}
+
+int sbe_inflight_list_keys(const void* table, const void* other, uint32_t flags, uint64_t min_value, uint32_t limit,
+                           const sbe_key_list_out* out, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    constexpr uint32_t kMember = SBE_LIST_IN_OTHER | SBE_LIST_NOT_IN_OTHER, kAns = SBE_LIST_ANSWERED | SBE_LIST_UNANSWERED;
+    if (!table || !out || !out->count || !workspace || limit > SBE_LIST_MAX) return SBE_EINVAL;
+    if (limit && (!out->key || !out->len || !out->value || !out->answered)) return SBE_EINVAL;
+    if ((flags & ~(kMember | kAns)) || (flags & kMember) == kMember || (flags & kAns) == kAns) return SBE_EINVAL;
+    if (((flags & kMember) != 0) != (other != nullptr) || other == table) return SBE_EINVAL;
+    if (misaligned(table, 63) || misaligned(other, 63) || misaligned(out->count, 7) || misaligned(out->value, 7) ||
+        misaligned(out->len, 3))
+        return SBE_EINVAL;
+    if (workspace_bytes < sbe_inflight_list_workspace_size(limit)) return SBE_ENOSPC;
+    Carver ws(workspace);
+    uint64_t* wg_pass = ws.take<uint64_t>(kDrListBlocks);
+    uint32_t* wg_n = ws.take<uint32_t>(kDrListBlocks);
+    DrCand* wg_list = ws.take<DrCand>((uint64_t)kDrListBlocks * limit);
+    const DrListArgs a{reinterpret_cast<const uint8_t*>(table), reinterpret_cast<const uint8_t*>(other), flags, min_value,
+                       limit, wg_list, wg_n, wg_pass, kDrListBlocks, out->count, out->key, out->len, out->value,
+                       out->answered};
+    hipLaunchKernelGGL(dr_list_scan, dim3(kDrListBlocks), dim3(kDrBlk), 0, s, a);
+    hipLaunchKernelGGL(dr_list_merge, dim3(1), dim3(kDrBlk), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+size_t sbe_latency_log_size(uint64_t capacity) { return lat_capacity_ok(capacity) ? (size_t)(64 + 16 * capacity) : 0; }
+
+int sbe_latency_log_init(void* log, size_t log_bytes, uint64_t capacity, void* stream) {
+    const size_t need = sbe_latency_log_size(capacity);
+    if (!log || misaligned(log, 63) || !need || log_bytes < need) return SBE_EINVAL;
+    hipLaunchKernelGGL(lat_init_header, dim3(1), dim3(kWave), 0, reinterpret_cast<hipStream_t>(stream),
+                       reinterpret_cast<uint8_t*>(log), capacity);
+    return record_hip(hipGetLastError());
+}
+
+size_t sbe_latency_append_workspace_size(uint64_t n) {
+    // the cursor pair, then one count per workgroup of kDrTile records
+    return (size_t)(64 + 4 * (((n ? n : 1) + kDrTile - 1) / kDrTile));
+}
+
+int sbe_latency_append(void* log, const uint8_t* code, const uint64_t* value, uint64_t n, uint64_t now_ns,
+                       uint64_t unit_ns, uint64_t tag_base, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!log || misaligned(log, 63) || n >= (1ull << 32)) return SBE_EINVAL;
+    if (n == 0) return SBE_OK;
+    if (!code || !value || !workspace || misaligned(value, 7) || misaligned(workspace, 7)) return SBE_EINVAL;
+    if (unit_ns < 1 || unit_ns > (1ull << 62)) return SBE_EINVAL;
+    if (workspace_bytes < sbe_latency_append_workspace_size(n)) return SBE_ENOSPC;
+    const uint32_t wgs = (uint32_t)((n + kDrTile - 1) / kDrTile);
+    Carver ws(workspace);
+    uint64_t* cursor = ws.take<uint64_t>(2);
+    uint32_t* blk = ws.take<uint32_t>(wgs);
+    const LatAppendArgs a{reinterpret_cast<uint8_t*>(log), code, value, n, now_ns, unit_ns, tag_base, cursor, blk, wgs};
+    hipLaunchKernelGGL(lat_append_count, dim3(wgs), dim3(kDrBlk), 0, s, a);
+    hipLaunchKernelGGL(lat_append_scan, dim3(1), dim3(kDrBlk), 0, s, a);
+    hipLaunchKernelGGL(lat_append_place, dim3(wgs), dim3(kDrBlk), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+size_t sbe_latency_report_workspace_size(uint64_t capacity) {
+    if (!lat_capacity_ok(capacity)) return 0;
+    // two (key, position) buffers and a 256-row histogram over the tiles, each piece on 16 bytes
+    return (size_t)(24 * capacity + 1024 * ((capacity + kDrTile - 1) / kDrTile) + 128);
+}
+
+int sbe_latency_report(const void* log, const double* pct, uint32_t n_pct, const sbe_latency_report_out* out,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!log || !out || !out->count || !out->stats || !workspace || n_pct > SBE_LAT_MAX_PCT) return SBE_EINVAL;
+    if (n_pct && (!pct || !out->pct_value || !out->pct_index)) return SBE_EINVAL;
+    if (misaligned(log, 63) || misaligned(out->count, 7) || misaligned(out->stats, 7) || misaligned(out->pct_value, 7) ||
+        misaligned(out->pct_index, 7) || misaligned(out->sorted, 7) || misaligned(out->order, 3))
+        return SBE_EINVAL;
+    LatReportArgs a{};
+    for (uint32_t p = 0; p < n_pct; ++p) {
+        if (!(pct[p] >= 0.0 && pct[p] <= 100.0)) return SBE_EINVAL;  // a NaN fails both
+        a.pct[p] = pct[p];
+    }
+    if (workspace_bytes < sbe_latency_report_workspace_size(1)) return SBE_ENOSPC;
+    // the most samples this workspace holds: the device compares the log's count with it
+    uint64_t lo = 1, hi = 1ull << 31;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (sbe_latency_report_workspace_size(mid) <= workspace_bytes)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    Carver ws(workspace);
+    a.s.log = reinterpret_cast<const uint8_t*>(log);
+    a.s.ws_cap = lo;
+    for (int b = 0; b < 2; ++b) a.s.key[b] = ws.take<uint64_t>(lo);
+    for (int b = 0; b < 2; ++b) a.s.idx[b] = ws.take<uint32_t>(lo);
+    a.s.hist = ws.take<uint32_t>(256 * ((lo + kDrTile - 1) / kDrTile));
+    a.n_pct = n_pct;
+    a.count = out->count;
+    a.stats = out->stats;
+    a.pct_value = out->pct_value;
+    a.pct_index = out->pct_index;
+    a.sorted = out->sorted;
+    a.order = out->order;
+    if (const int rc = record_hip(hipMemsetAsync(out->stats, 0, 24, s))) return rc;
+    for (uint32_t p = 0; p < 8; ++p) {
+        hipLaunchKernelGGL(lat_sort_hist, dim3(kDrSortBlocks), dim3(kDrBlk), 0, s, a.s, p);
+        hipLaunchKernelGGL(lat_sort_scan, dim3(1), dim3(kDrBlk), 0, s, a.s);
+        hipLaunchKernelGGL(lat_sort_scatter, dim3(kDrSortBlocks), dim3(kDrBlk), 0, s, a.s, p);
+    }
+    hipLaunchKernelGGL(lat_report_final, dim3(kDrSortBlocks), dim3(kDrBlk), 0, s, a);
     return record_hip(hipGetLastError());
 }
 

@@ -3630,17 +3630,78 @@ struct DeliveryTracker::Impl {
     std::unordered_set<std::string> long_clients;
     std::unordered_map<std::string, LongSent> long_sent;
     size_t long_answered = 0;
+    // the recorded latencies in nanoseconds: a device log (sbe_latency_*), fed behind every lookup
+    DevBuf log, log_ws, log_stage, rep;
+    uint64_t log_cap = 0, log_bound = 0;  // samples it holds; an upper bound of its count
+    uint64_t calls = 0;                   // on_batch / on_message calls so far: the high half of a tag
+    std::vector<std::pair<size_t, uint64_t>> long_samples;  // (record, send time) of the running call's long ids
 
     void sync() { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
 
-    // note (message ids), note (client ids), lookup (sent) over keys that lie in a device buffer;
-    // `res` is device memory of TrackLayout(n).total bytes
+    // room for n more samples, by reallocate-and-copy when needed
+    void log_reserve(uint64_t n) {
+        if (log_cap && log_bound + n <= log_cap) return;
+        if (log_cap) {
+            uint64_t h[3];
+            hip_check(hipMemcpyAsync(h, log.p, 24, hipMemcpyDeviceToHost, stream), "D2H");
+            sync();
+            log_bound = h[1];
+            if (log_bound + n <= log_cap) return;
+        }
+        uint64_t ncap = log_cap ? log_cap : 1024;
+        while (log_bound + n > ncap) ncap *= 2;
+        if (ncap > (1ull << 31)) throw std::runtime_error("sbecodec: the latency log cannot grow past 2^31 samples");
+        DevBuf fresh;
+        fresh.need(sbe_latency_log_size(ncap));
+        if (sbe_latency_log_init(fresh.p, sbe_latency_log_size(ncap), ncap, stream) != SBE_OK) fail("sbe_latency_log_init");
+        if (log_cap) {  // count and dropped, the latencies, the tags
+            auto copy = [&](size_t to, size_t from, size_t len) {
+                hip_check(hipMemcpyAsync(fresh.b() + to, log.b() + from, len, hipMemcpyDeviceToDevice, stream), "D2D");
+            };
+            copy(8, 8, 16);
+            copy(64, 64, 8 * log_bound);
+            copy(64 + 8 * ncap, 64 + 8 * log_cap, 8 * log_bound);
+        }
+        sync();
+        std::swap(log.p, fresh.p);
+        std::swap(log.cap, fresh.cap);
+        log_cap = ncap;
+    }
+
+    // one sample per SBE_SENT_FIRST record of a lookup's device results
+    void log_append(const uint8_t* code, const uint64_t* value, size_t n, uint64_t now_ns) {
+        const size_t wsb = sbe_latency_append_workspace_size(n);
+        log_ws.need(wsb);
+        if (sbe_latency_append(log.p, code, value, n, now_ns, 1, calls << 32, log_ws.p, wsb, stream) != SBE_OK)
+            fail("sbe_latency_append");
+    }
+
+    // the samples settle() took from long_sent, as a second append with the records' own indices
+    void log_append_long(size_t n, uint64_t now_ns) {
+        if (long_samples.empty()) return;
+        const size_t o_code = 8 * n;
+        std::vector<uint8_t> host(o_code + n, 0);  // value [n] u64 | code [n]: SBE_SENT_NONE but for the samples
+        for (const auto& s : long_samples) {
+            std::memcpy(host.data() + 8 * s.first, &s.second, 8);
+            host[o_code + s.first] = SBE_SENT_FIRST;
+        }
+        log_stage.need(host.size());
+        hip_check(hipMemcpyAsync(log_stage.p, host.data(), host.size(), hipMemcpyHostToDevice, stream), "H2D");
+        log_append(log_stage.b() + o_code, reinterpret_cast<const uint64_t*>(log_stage.p), n, now_ns);
+        sync();  // `host` goes out of scope
+        long_samples.clear();
+    }
+
+    // note (message ids), note (client ids), lookup (sent) over keys that lie in a device buffer,
+    // and the lookup's latencies into the log; `res` is device memory of TrackLayout(n).total bytes
     void track(const uint8_t* buf, uint64_t buf_bytes, const uint64_t* mpos, const uint32_t* mlen, const uint64_t* cpos,
-               const uint32_t* clen, size_t n, uint8_t* res, TrackResults& r) {
+               const uint32_t* clen, size_t n, uint8_t* res, TrackResults& r, uint64_t now_ns) {
         const TrackLayout L(n);
         const size_t wsb = sbe_inflight_workspace_size(n);
         msgs.reserve(n, stream);
         clients.reserve(n, stream);
+        log_reserve(n);  // a record gives at most one sample, from the table or from long_sent
+        log_bound += n;
         if (sbe_inflight_note_keys(msgs.p(), buf, buf_bytes, mpos, mlen, n, res + L.mcode,
                                    reinterpret_cast<uint32_t*>(res + L.mcount), nullptr, res + L.ws, wsb, stream) != SBE_OK)
             fail("sbe_inflight_note_keys");
@@ -3650,6 +3711,7 @@ struct DeliveryTracker::Impl {
         if (sbe_inflight_lookup_keys(sends.p(), buf, buf_bytes, cpos, clen, n, res + L.scode,
                                      reinterpret_cast<uint64_t*>(res + L.sval), nullptr, res + L.ws, wsb, stream) != SBE_OK)
             fail("sbe_inflight_lookup_keys");
+        log_append(res + L.scode, reinterpret_cast<const uint64_t*>(res + L.sval), n, now_ns);
         msgs.used_bound += n;
         clients.used_bound += n;
         r.mcode.resize(n);
@@ -3692,6 +3754,7 @@ struct DeliveryTracker::Impl {
                 ++long_answered;
                 d.latency_recorded = true;
                 d.latency_ns = (int64_t)now_ns - (int64_t)it->second.ts;
+                long_samples.emplace_back(i, it->second.ts);
             }
         } else {
             d.was_sent = r.scode[i] == SBE_SENT_FIRST || r.scode[i] == SBE_SENT_REPEAT;
@@ -3745,6 +3808,136 @@ void DeliveryTracker::clear_duplicate_tracking() {
     if (sbe_inflight_reset_values(m.msgs.p(), m.stream) != SBE_OK) fail("sbe_inflight_reset_values");
     m.sync();
     for (auto& kv : m.long_msgs) kv.second = 1;
+}
+
+namespace {
+// The first `limit` entries of `table` that pass (sbe_inflight_list_keys) merged with `host`, the
+// passing ids the tables cannot hold: both in std::string order, so the merge looks at no more
+// than limit + host.size() entries.
+IdList list_ids(const InfTable& table, const InfTable* other, uint64_t min_value, size_t limit, std::vector<IdEntry> host,
+                DevBuf& dev, hipStream_t stream) {
+    if (limit > SBE_LIST_MAX) throw std::invalid_argument("DeliveryTracker: a list holds at most SBE_LIST_MAX ids");
+    const uint32_t k = (uint32_t)limit;
+    const size_t o_key = 64, o_len = o_key + al64(SBE_INFLIGHT_KEY_MAX * SBE_LIST_MAX), o_val = o_len + 4 * SBE_LIST_MAX,
+                 o_ans = o_val + 8 * SBE_LIST_MAX, o_ws = o_ans + SBE_LIST_MAX, wsb = sbe_inflight_list_workspace_size(k);
+    dev.need(o_ws + wsb);
+    uint8_t* d = dev.b();
+    const sbe_key_list_out out{reinterpret_cast<uint64_t*>(d), d + o_key, reinterpret_cast<uint32_t*>(d + o_len),
+                               reinterpret_cast<uint64_t*>(d + o_val), d + o_ans};
+    if (sbe_inflight_list_keys(table.p(), other ? other->p() : nullptr, other ? SBE_LIST_NOT_IN_OTHER : 0, min_value, k, &out,
+                               d + o_ws, wsb, stream) != SBE_OK)
+        fail("sbe_inflight_list_keys");
+    std::vector<uint8_t> back(o_ans);
+    hip_check(hipMemcpyAsync(back.data(), d, o_ans, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    uint64_t count;
+    std::memcpy(&count, back.data(), 8);
+    const size_t rows = (size_t)std::min<uint64_t>(count, k);
+    std::vector<IdEntry> listed(rows);
+    for (size_t j = 0; j < rows; ++j) {
+        uint32_t len;
+        std::memcpy(&len, back.data() + o_len + 4 * j, 4);
+        listed[j].id.assign(reinterpret_cast<const char*>(back.data() + o_key + SBE_INFLIGHT_KEY_MAX * j), len);
+        std::memcpy(&listed[j].value, back.data() + o_val + 8 * j, 8);
+    }
+    std::sort(host.begin(), host.end(), [](const IdEntry& a, const IdEntry& b) { return a.id < b.id; });
+    IdList res;
+    res.total = (size_t)count + host.size();
+    res.first.resize(listed.size() + host.size());
+    std::merge(listed.begin(), listed.end(), host.begin(), host.end(), res.first.begin(),
+               [](const IdEntry& a, const IdEntry& b) { return a.id < b.id; });
+    if (res.first.size() > limit) res.first.resize(limit);
+    return res;
+}
+}  // namespace
+
+IdList DeliveryTracker::missing_ids(std::size_t limit) const {
+    Impl& m = *impl_;
+    std::vector<IdEntry> host;
+    for (const auto& kv : m.long_sent)
+        if (!m.long_clients.count(kv.first)) host.push_back({kv.first, kv.second.ts});
+    return list_ids(m.sends, &m.clients, 0, limit, std::move(host), m.rep, m.stream);
+}
+
+IdList DeliveryTracker::extra_ids(std::size_t limit) const {
+    Impl& m = *impl_;
+    std::vector<IdEntry> host;
+    for (const std::string& id : m.long_clients)
+        if (!m.long_sent.count(id)) host.push_back({id, 0});
+    return list_ids(m.clients, &m.sends, 0, limit, std::move(host), m.rep, m.stream);
+}
+
+IdList DeliveryTracker::redelivered_ids(std::size_t limit) const {
+    Impl& m = *impl_;
+    std::vector<IdEntry> host;
+    for (const auto& kv : m.long_msgs)
+        if (kv.second >= 2) host.push_back({kv.first, kv.second});
+    IdList res = list_ids(m.msgs, nullptr, 2, limit, std::move(host), m.rep, m.stream);
+    for (IdEntry& e : res.first) --e.value;  // deliveries -> redeliveries
+    return res;
+}
+
+LatencyReport DeliveryTracker::latency_report(const std::vector<double>& pcts, std::uint64_t unit_ns, bool want_rows) const {
+    Impl& m = *impl_;
+    if (pcts.size() > SBE_LAT_MAX_PCT || unit_ns < 1 || unit_ns > (1ull << 62))
+        throw std::invalid_argument("DeliveryTracker::latency_report: at most 16 percentiles, unit_ns in 1 .. 2^62");
+    for (double p : pcts)
+        if (!(p >= 0.0 && p <= 100.0)) throw std::invalid_argument("DeliveryTracker::latency_report: a percentile outside [0, 100]");
+    LatencyReport res;
+    res.percentiles.assign(pcts.size(), 0);
+    if (!m.log_cap) return res;  // nothing was ever tracked
+    const bool rows = want_rows || unit_ns != 1;  // the sorted samples are needed on the host
+    const size_t np = SBE_LAT_MAX_PCT, o_stats = 64, o_pv = 128, o_pi = o_pv + 8 * np, o_sorted = o_pi + 8 * np,
+                 o_order = o_sorted + (rows ? al64(8 * m.log_cap) : 0), o_ws = o_order + (rows ? al64(4 * m.log_cap) : 0),
+                 wsb = sbe_latency_report_workspace_size(m.log_cap);
+    m.rep.need(o_ws + wsb);
+    uint8_t* d = m.rep.b();
+    const sbe_latency_report_out out{reinterpret_cast<uint64_t*>(d), reinterpret_cast<int64_t*>(d + o_stats),
+                                     reinterpret_cast<int64_t*>(d + o_pv), reinterpret_cast<uint64_t*>(d + o_pi),
+                                     rows ? reinterpret_cast<int64_t*>(d + o_sorted) : nullptr,
+                                     rows ? reinterpret_cast<uint32_t*>(d + o_order) : nullptr};
+    if (sbe_latency_report(m.log.p, pcts.data(), (uint32_t)pcts.size(), &out, d + o_ws, wsb, m.stream) != SBE_OK)
+        fail("sbe_latency_report");
+    std::vector<uint8_t> head(o_sorted);
+    hip_check(hipMemcpyAsync(head.data(), d, o_sorted, hipMemcpyDeviceToHost, m.stream), "D2H");
+    m.sync();
+    int64_t stats[3];
+    std::memcpy(&res.count, head.data(), 8);
+    std::memcpy(stats, head.data() + o_stats, 24);
+    const int64_t unit = (int64_t)unit_ns;
+    res.sum = stats[0];
+    res.min = stats[1] / unit;
+    res.max = stats[2] / unit;
+    for (size_t p = 0; p < pcts.size(); ++p) {
+        int64_t v;
+        std::memcpy(&v, head.data() + o_pv + 8 * p, 8);
+        res.percentiles[p] = v / unit;
+    }
+    if (rows && res.count) {
+        const size_t n = (size_t)res.count;
+        std::vector<int64_t> sorted(n);
+        hip_check(hipMemcpyAsync(sorted.data(), d + o_sorted, 8 * n, hipMemcpyDeviceToHost, m.stream), "D2H");
+        std::vector<uint32_t> order;
+        std::vector<uint64_t> tags;
+        if (want_rows) {
+            order.resize(n);
+            tags.resize(n);  // positions below the count
+            hip_check(hipMemcpyAsync(order.data(), d + o_order, 4 * n, hipMemcpyDeviceToHost, m.stream), "D2H");
+            hip_check(hipMemcpyAsync(tags.data(), m.log.b() + 64 + 8 * m.log_cap, 8 * n, hipMemcpyDeviceToHost, m.stream), "D2H");
+        }
+        m.sync();
+        if (unit_ns != 1) {  // the sum of the divided samples, mod 2^64
+            uint64_t s = 0;
+            for (int64_t v : sorted) s += (uint64_t)(v / unit);
+            res.sum = (int64_t)s;
+        }
+        if (want_rows) {
+            res.rows.resize(n);
+            for (size_t j = 0; j < n; ++j) res.rows[j] = LatencyRow{sorted[n - 1 - j] / unit, tags[order[n - 1 - j]]};
+        }
+    }
+    res.avg = res.count ? (double)res.sum / (double)res.count : 0.0;
+    return res;
 }
 
 void DeliveryTracker::note_sent(const std::vector<std::string>& ids, std::uint64_t ts_ns) {
@@ -3815,8 +4008,10 @@ Delivery DeliveryTracker::on_message(const ParseResult& result, std::uint64_t no
     TrackResults r;
     m.track(m.in.b() + o_key, mid.size() + cid.size(), reinterpret_cast<const uint64_t*>(m.in.p),
             reinterpret_cast<const uint32_t*>(m.in.b() + o_mlen), reinterpret_cast<const uint64_t*>(m.in.b() + o_cpos),
-            reinterpret_cast<const uint32_t*>(m.in.b() + o_clen), 1, m.out.b(), r);
+            reinterpret_cast<const uint32_t*>(m.in.b() + o_clen), 1, m.out.b(), r, now_ns);
     m.settle(d, mid, r, 0, now_ns);
+    m.log_append_long(1, now_ns);
+    ++m.calls;
     return d;
 }
 
@@ -3952,7 +4147,7 @@ std::vector<Delivery> DeliveryTracker::on_batch(const ParsedBatch& batch, std::u
     TrackResults tr;
     m.track(di + o_data, bytes + extra.size(), reinterpret_cast<const uint64_t*>(dq + k_mpos),
             reinterpret_cast<const uint32_t*>(dq + k_mlen), reinterpret_cast<const uint64_t*>(dq + k_cpos),
-            reinterpret_cast<const uint32_t*>(dq + k_clen), n, dq + o_res, tr);
+            reinterpret_cast<const uint32_t*>(dq + k_clen), n, dq + o_res, tr, now_ns);
     bool long_ids = false;
     for (size_t i = 0; i < n; ++i) {
         if (!sel[i]) continue;
@@ -3960,6 +4155,8 @@ std::vector<Delivery> DeliveryTracker::on_batch(const ParsedBatch& batch, std::u
         m.settle(res[i], mid, tr, i, now_ns);
         long_ids |= mid.size() > SBE_INFLIGHT_KEY_MAX;
     }
+    m.log_append_long(n, now_ns);
+    ++m.calls;
     if (long_ids)  // as for the table's ids: the count recorded after the whole batch
         for (size_t i = 0; i < n; ++i)
             if (sel[i] && mlen[i] != SBE_NO_KEY && mlen[i] > SBE_INFLIGHT_KEY_MAX && res[i].already_processed)

@@ -555,6 +555,33 @@ struct Delivery {
     std::int64_t latency_ns = 0;            // now_ns - send time, when latency_recorded
 };
 
+// The first ids of one of the example's reports, in std::set<std::string> order, and how many
+// there are in all (printMessageComparison :130-204 prints ten and "... and N more").
+struct IdEntry {
+    std::string id;
+    std::uint64_t value = 0;  // missing_ids: the send time; extra_ids: the id's deliveries (0 for an id over
+                              // SBE_INFLIGHT_KEY_MAX bytes); redelivered_ids: its redeliveries, as
+                              // duplicate_delivery_counts (:83-90) holds them
+};
+struct IdList {
+    std::size_t total = 0;
+    std::vector<IdEntry> first;
+};
+
+// printLatencyReport (:276-353) over the latencies the tracker recorded.
+struct LatencyRow {
+    std::int64_t latency = 0;  // in units of unit_ns
+    std::uint64_t tag = 0;     // (ordinal of the on_batch / on_message call among those that reached the
+                               // tables: a non-empty batch, a selected message) << 32 | record index in it
+};
+struct LatencyReport {
+    std::uint64_t count = 0;
+    std::int64_t sum = 0, min = 0, max = 0;  // sum mod 2^64; all 0 without samples
+    double avg = 0.0;                        // (double)sum / (double)count, :334
+    std::vector<std::int64_t> percentiles;   // one per requested pct, by the example's rank (:322-326)
+    std::vector<LatencyRow> rows;            // on request: every sample, slowest first (:304)
+};
+
 // The tables that callback keeps across calls, on the device: received_message_ids with the
 // per-id counts of duplicate_delivery_counts, received_client_order_ids, and the publisher's
 // sent_client_order_ids / client_order_send_time (:455-459, :498-501), three sbe_inflight_* tables
@@ -591,6 +618,23 @@ public:
     std::size_t extra() const;
     void clear_duplicate_tracking();  // :70-73: the redelivery counts start again
     std::uint64_t rehashes() const;
+    // The reports the example prints from these sets, read on the device (sbe_inflight_list_keys,
+    // sbe_latency_report) without copying a table back.  Each list holds the first `limit` ids
+    // (at most SBE_LIST_MAX = 64; std::invalid_argument beyond) in std::string order and the
+    // number of all of them; ids over SBE_INFLIGHT_KEY_MAX bytes are merged in from the host sets.
+    IdList missing_ids(std::size_t limit = 10) const;      // sent and never received (:153-157)
+    IdList extra_ids(std::size_t limit = 10) const;        // received and never sent (:158-162)
+    IdList redelivered_ids(std::size_t limit = 10) const;  // message ids delivered more than once (:83-90)
+    // Every latency on_batch / on_message recorded goes to a log on the device, in nanoseconds,
+    // right behind the lookup that found it; the log grows as the tables do.  The report divides
+    // by unit_ns as duration_cast does (truncation toward zero; 1 .. 2^62, 1000000: the example's
+    // milliseconds): min, max and the percentiles are the divided entries of the sorted
+    // nanoseconds, which is what sorting the divided samples gives; the sum of divided samples is
+    // taken on the host from the sorted copy when unit_ns != 1.  pcts: at most 16 values in
+    // [0, 100].  want_rows: every sample slowest first; equal latencies by descending nanoseconds,
+    // then later records first.
+    LatencyReport latency_report(const std::vector<double>& pcts = {75.0, 80.0, 90.0, 95.0, 99.0, 99.9, 99.99},
+                                 std::uint64_t unit_ns = 1000000, bool want_rows = false) const;
 
 private:
     struct Impl;

@@ -142,6 +142,14 @@ class _DeliveryKeyOut(ctypes.Structure):
                                                "oid_len", "oid_kind", "selected", "totals")]
 
 
+class _KeyListOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("count", "key", "len", "value", "answered")]
+
+
+class _LatencyReportOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("count", "stats", "pct_value", "pct_index", "sorted", "order")]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise SbeError(f"{LIB_PATH} is missing: build it with `make -C aeron-cluster-client-cpp_amd` "
@@ -261,6 +269,26 @@ def _load():
     lib.sbe_delivery_keys.restype = ctypes.c_int
     lib.sbe_delivery_keys.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_Decoded), ctypes.c_void_p,
                                       ctypes.POINTER(_JsonOut), ctypes.POINTER(_DeliveryKeyOut), ctypes.c_void_p]
+    lib.sbe_inflight_list_workspace_size.restype = ctypes.c_size_t
+    lib.sbe_inflight_list_workspace_size.argtypes = [ctypes.c_uint32]
+    lib.sbe_inflight_list_keys.restype = ctypes.c_int
+    lib.sbe_inflight_list_keys.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                           ctypes.c_uint32, ctypes.POINTER(_KeyListOut), ctypes.c_void_p,
+                                           ctypes.c_size_t, ctypes.c_void_p]
+    for name in ("sbe_latency_log_size", "sbe_latency_append_workspace_size", "sbe_latency_report_workspace_size"):
+        f = getattr(lib, name)
+        f.restype = ctypes.c_size_t
+        f.argtypes = [ctypes.c_uint64]
+    lib.sbe_latency_log_init.restype = ctypes.c_int
+    lib.sbe_latency_log_init.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p]
+    lib.sbe_latency_append.restype = ctypes.c_int
+    lib.sbe_latency_append.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                       ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                       ctypes.c_size_t, ctypes.c_void_p]
+    lib.sbe_latency_report.restype = ctypes.c_int
+    lib.sbe_latency_report.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_uint32,
+                                       ctypes.POINTER(_LatencyReportOut), ctypes.c_void_p, ctypes.c_size_t,
+                                       ctypes.c_void_p]
     lib.sbe_profile_enable.restype = ctypes.c_int
     lib.sbe_order_json_workspace_size.argtypes = [ctypes.c_uint64]
     lib.sbe_order_json_workspace_size.restype = ctypes.c_size_t
@@ -967,6 +995,58 @@ class KeyLookups:
                 "totals": self.totals.cpu().numpy().view(np.uint64)}
 
 
+# sbe_inflight_list_keys / sbe_latency_*: delivery reports
+LIST_MAX = 64
+LIST_IN_OTHER, LIST_NOT_IN_OTHER, LIST_ANSWERED, LIST_UNANSWERED = 1, 2, 4, 8
+LAT_MAX_PCT = 16
+REPORT_PERCENTILES = (75.0, 80.0, 90.0, 95.0, 99.0, 99.9, 99.99)  # printLatencyReport's
+
+
+@dataclass
+class KeyList:
+    count: torch.Tensor     # int64 [1]  (u64) entries that pass the filter, listed or not
+    key: torch.Tensor       # uint8 [limit, 40]  zero-padded key bytes
+    len: torch.Tensor       # int32 [limit]  (u32)
+    value: torch.Tensor     # int64 [limit]  (u64) the slot's value
+    answered: torch.Tensor  # uint8 [limit]
+
+    def numpy(self):
+        import numpy as np
+        return {"count": self.count.cpu().numpy().view(np.uint64), "key": self.key.cpu().numpy(),
+                "len": self.len.cpu().numpy().view(np.uint32), "value": self.value.cpu().numpy().view(np.uint64),
+                "answered": self.answered.cpu().numpy()}
+
+    def rows(self):
+        """The listed entries as (key bytes, value, answered) (synchronises)."""
+        d = self.numpy()
+        n = min(int(d["count"][0]), len(d["len"]))
+        return [(d["key"][j, : int(d["len"][j])].tobytes(), int(d["value"][j]), bool(d["answered"][j])) for j in range(n)]
+
+
+@dataclass
+class LatencyReport:
+    count: torch.Tensor         # int64 [1]  (u64) samples in the log
+    stats: torch.Tensor         # int64 [3]  sum (mod 2^64), min, max
+    pct_value: torch.Tensor     # int64 [n_pct]
+    pct_index: torch.Tensor     # int64 [n_pct]  (u64) the index the value was read from
+    sorted: torch.Tensor | None  # int64 [capacity]: the first count entries, ascending
+    order: torch.Tensor | None   # int32 [capacity]  (u32) log position of sorted[j]
+
+    def numpy(self):
+        import numpy as np
+        d = {"count": self.count.cpu().numpy().view(np.uint64), "stats": self.stats.cpu().numpy(),
+             "pct_value": self.pct_value.cpu().numpy(), "pct_index": self.pct_index.cpu().numpy().view(np.uint64)}
+        if self.sorted is not None:
+            d["sorted"] = self.sorted.cpu().numpy()
+            d["order"] = self.order.cpu().numpy().view(np.uint32)
+        return d
+
+    def average(self) -> float:
+        """(double)sum / (double)count, as printLatencyReport :334 (synchronises); 0.0 for no samples."""
+        n = int(self.count.cpu().numpy().view("<u8")[0])
+        return float(int(self.stats[0])) / float(n) if n else 0.0
+
+
 _DELIVERY_KEYS = (("msg_pos", "int64"), ("msg_len", "int32"), ("coid_pos", "int64"), ("coid_len", "int32"),
                   ("coid_kind", "uint8"), ("oid_pos", "int64"), ("oid_len", "int32"), ("oid_kind", "uint8"),
                   ("selected", "uint8"), ("totals", "int64"))
@@ -1037,7 +1117,7 @@ class Inflight:
             raw = torch.empty(size + 64, dtype=torch.uint8, device=self.device)
             lead = (-raw.data_ptr()) % 64
             self.table = raw[lead: lead + size]
-        self._ws = None
+        self._ws = self._list_ws = None
         self.clear(stream)
 
     @staticmethod
@@ -1160,6 +1240,40 @@ class Inflight:
         """clear_duplicate_tracking (:70-73): every live entry back to one delivery, its count to 0."""
         _check(lib().sbe_inflight_reset_values(_ptr(self.table), _stream(stream)), "sbe_inflight_reset_values")
 
+    def list_keys(self, other: "Inflight | None" = None, flags: int = 0, min_value: int = 0, limit: int = 10,
+                  out: KeyList | None = None, workspace=None, stream=None) -> KeyList:
+        """The entries that pass a filter, smallest keys first in std::string order
+        (printMessageComparison / printClientOrderAudit, examples/pubsub_reconnect_test.cpp:130-274):
+        flags LIST_IN_OTHER / LIST_NOT_IN_OTHER against the live keys of `other`, LIST_ANSWERED /
+        LIST_UNANSWERED, and value >= min_value (2 on a table of message ids: the redelivered ones).
+        count is every passing entry; rows past min(count, limit) are left as they were.  Neither
+        table is modified."""
+        limit = int(limit)
+        if not 0 <= limit <= LIST_MAX:
+            raise SbeError(f"Inflight.list_keys: limit {limit} is not in 0 .. {LIST_MAX}")
+        if out is None:
+            rows = max(limit, 1)
+            out = KeyList(torch.empty(1, dtype=torch.int64, device=self.device),
+                          torch.zeros((rows, INFLIGHT_KEY_MAX), dtype=torch.uint8, device=self.device),
+                          torch.zeros(rows, dtype=torch.int32, device=self.device),
+                          torch.zeros(rows, dtype=torch.int64, device=self.device),
+                          torch.zeros(rows, dtype=torch.uint8, device=self.device))
+        need = int(lib().sbe_inflight_list_workspace_size(limit))
+        if workspace is not None:
+            ws = _dev(workspace, torch.uint8, "workspace")
+        else:
+            if self._list_ws is None or self._list_ws.numel() < need:
+                self._list_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._list_ws
+        o = _KeyListOut(*(getattr(out, k).data_ptr() for k in ("count", "key", "len", "value", "answered")))
+        rc = lib().sbe_inflight_list_keys(_ptr(self.table), None if other is None else _ptr(other.table), int(flags),
+                                          int(min_value), limit, ctypes.byref(o), _ptr(ws), int(ws.numel()),
+                                          _stream(stream))
+        _check(rc, "sbe_inflight_list_keys")
+        if limit < out.len.numel():
+            out = KeyList(out.count, out.key[:limit], out.len[:limit], out.value[:limit], out.answered[:limit])
+        return out
+
     def rehash(self, capacity: int, stream=None, tag_bits=None) -> "Inflight":
         """A new table of `capacity` slots holding this one's live entries (erased slots reclaimed)."""
         live = self.stats()["live"]
@@ -1168,6 +1282,103 @@ class Inflight:
         new = Inflight(capacity, self.device, self.tag_bits if tag_bits is None else tag_bits, stream=stream)
         _check(lib().sbe_inflight_rehash(_ptr(self.table), _ptr(new.table), _stream(stream)), "sbe_inflight_rehash")
         return new
+
+
+class LatencyLog:
+    """The latencies the subscriber's callback records once per client_order_id
+    (examples/pubsub_reconnect_test.cpp:669-691) as a log on the device: `capacity` samples
+    (1 .. 2^31) of a latency and a tag.  It owns the log tensor and its workspaces and serves one
+    stream at a time."""
+
+    def __init__(self, capacity: int, device, stream=None, log=None):
+        size = int(lib().sbe_latency_log_size(int(capacity)))
+        if size == 0:
+            raise SbeError(f"LatencyLog: capacity {capacity} is not in 1 .. 2^31")
+        self.capacity, self.device = int(capacity), torch.device(device)
+        if log is not None:  # the caller's memory (uint8, 64-byte aligned, at least log_bytes(capacity))
+            self.log = _dev(log, torch.uint8, "log")[:size]
+        else:
+            raw = torch.empty(size + 64, dtype=torch.uint8, device=self.device)
+            lead = (-raw.data_ptr()) % 64
+            self.log = raw[lead: lead + size]
+        self._ws = self._report_ws = None
+        self.clear(stream)
+
+    @staticmethod
+    def log_bytes(capacity: int) -> int:
+        return int(lib().sbe_latency_log_size(int(capacity)))
+
+    def clear(self, stream=None):
+        """Back to an empty log (sbe_latency_log_init)."""
+        _check(lib().sbe_latency_log_init(_ptr(self.log), int(self.log.numel()), self.capacity, _stream(stream)),
+               "sbe_latency_log_init")
+
+    def append(self, lookups: KeyLookups, now_ns: int, unit_ns: int = 1_000_000, tag_base: int = 0, n=None,
+               workspace=None, stream=None):
+        """One sample per SENT_FIRST record of a lookup_keys result, in index order:
+        lat = (now_ns - value) / unit_ns as signed C++ division, tag = tag_base + index.  Samples
+        past the capacity are counted in header()["dropped"]."""
+        code = _dev(lookups.code, torch.uint8, "code")
+        value = _dev(lookups.value, torch.int64, "value")
+        if n is None:
+            n = int(code.numel())
+        if min(code.numel(), value.numel()) < n:
+            raise SbeError("LatencyLog.append: code or value hold fewer than n records")
+        need = int(lib().sbe_latency_append_workspace_size(n))
+        if workspace is not None:
+            ws = _dev(workspace, torch.uint8, "workspace")
+        else:
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._ws
+        mask = 2 ** 64 - 1
+        rc = lib().sbe_latency_append(_ptr(self.log), _ptr(code), _ptr(value), n, int(now_ns) & mask, int(unit_ns),
+                                      int(tag_base) & mask, _ptr(ws), int(ws.numel()), _stream(stream))
+        _check(rc, "sbe_latency_append")
+
+    def report(self, pct=REPORT_PERCENTILES, want_order: bool = False, out: LatencyReport | None = None,
+               workspace=None, stream=None) -> LatencyReport:
+        """printLatencyReport (:276-353): count, {sum, min, max}, and for every pct the sample at the
+        example's own rank (:322-326) with the index it was read from; want_order adds the samples
+        ascending by (latency, log position) and the log positions in that order."""
+        pct = [float(p) for p in pct]
+        if len(pct) > LAT_MAX_PCT:
+            raise SbeError(f"LatencyLog.report: more than {LAT_MAX_PCT} percentiles")
+        if out is None:
+            i64 = dict(dtype=torch.int64, device=self.device)
+            out = LatencyReport(torch.empty(1, **i64), torch.empty(3, **i64), torch.empty(max(len(pct), 1), **i64),
+                                torch.empty(max(len(pct), 1), **i64),
+                                torch.zeros(self.capacity, **i64) if want_order else None,
+                                torch.zeros(self.capacity, dtype=torch.int32, device=self.device) if want_order else None)
+        need = int(lib().sbe_latency_report_workspace_size(self.capacity))
+        if workspace is not None:
+            ws = _dev(workspace, torch.uint8, "workspace")
+        else:
+            if self._report_ws is None:
+                self._report_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._report_ws
+        o = _LatencyReportOut(out.count.data_ptr(), out.stats.data_ptr(), out.pct_value.data_ptr(),
+                              out.pct_index.data_ptr(), None if out.sorted is None else out.sorted.data_ptr(),
+                              None if out.order is None else out.order.data_ptr())
+        table = (ctypes.c_double * max(len(pct), 1))(*pct)
+        rc = lib().sbe_latency_report(_ptr(self.log), table, len(pct), ctypes.byref(o), _ptr(ws), int(ws.numel()),
+                                      _stream(stream))
+        _check(rc, "sbe_latency_report")
+        if len(pct) < out.pct_value.numel():
+            out = LatencyReport(out.count, out.stats, out.pct_value[: len(pct)], out.pct_index[: len(pct)], out.sorted,
+                                out.order)
+        return out
+
+    def header(self) -> dict:
+        """{capacity, count, dropped} read back from the log's header (synchronises)."""
+        h = self.log[:24].cpu().numpy().view("<u8")
+        return {"capacity": int(h[0]), "count": int(h[1]), "dropped": int(h[2])}
+
+    def samples(self):
+        """(lat int64 [count], tag uint64 [count]) copied back (synchronises)."""
+        n = self.header()["count"]
+        body = self.log[64:].cpu().numpy()
+        return body[: 8 * n].view("<i8").copy(), body[8 * self.capacity:][: 8 * n].view("<u8").copy()
 
 
 @dataclass

@@ -82,6 +82,14 @@
  *                                  (sbe_inflight_reset_values: clear_duplicate_tracking, :70-73)
  * sbe_delivery_keys()             the three keys of those lookups per record: message_id and the
  *                                  client_order_id / order_id the callback picks, :592-619
+ * sbe_inflight_list_keys()        printMessageComparison examples/pubsub_reconnect_test.cpp:130-204 and
+ *                                  printClientOrderAudit :206-274: the ids sent and never received, or
+ *                                  received and never sent, the first ones in std::set order; with a
+ *                                  least value of 2, the ids of duplicate_delivery_counts (:83-90)
+ * sbe_latency_append()            the latency the callback records per client_order_id (:669-691), kept
+ *                                  in a device log (sbe_latency_log_size, _log_init)
+ * sbe_latency_report()            printLatencyReport :276-353: the sorted latencies, sum, min, max and
+ *                                  the percentiles by its own rank formula (:322-326)
  * sbe_json_extract_batch()        what a consumer's callback reads out of result.payload: the
  *                                  Json::parseFromStream + isMember / operator[] lookups of
  *                                  examples/pubsub_reconnect_test.cpp:576-620 (again :1142-1160) and of
@@ -822,6 +830,105 @@ typedef struct sbe_delivery_key_out { /* device arrays of n elements; u64 8-B, u
  * n >= 2^32, an array below its alignment. */
 int sbe_delivery_keys(const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec, const uint8_t* select,
                       const sbe_json_out* ids, const sbe_delivery_key_out* out, void* stream);
+
+/* ================================ delivery reports ================================ */
+/* The read side of the tables above: what examples/pubsub_reconnect_test.cpp prints from its sets
+ * (printMessageComparison :130-204, printClientOrderAudit :206-274, printLatencyReport :276-353)
+ * without copying a table back.  No call here modifies a table. */
+#define SBE_LIST_MAX 64u
+#define SBE_LIST_IN_OTHER 0x1u     /* keep keys that are live in `other` */
+#define SBE_LIST_NOT_IN_OTHER 0x2u /* keep keys that are not live in `other` */
+#define SBE_LIST_ANSWERED 0x4u     /* keep entries with the answered bit */
+#define SBE_LIST_UNANSWERED 0x8u   /* keep entries without it */
+typedef struct sbe_key_list_out { /* device arrays */
+    uint64_t* count;   /* [1] every LIVE entry that passes the filter, listed or not (8-B aligned) */
+    uint8_t* key;      /* [limit][SBE_INFLIGHT_KEY_MAX] zero-padded key bytes */
+    uint32_t* len;     /* [limit] (4-B aligned) */
+    uint64_t* value;   /* [limit] the slot's 8-byte value (8-B aligned) */
+    uint8_t* answered; /* [limit] 0 / 1 */
+} sbe_key_list_out;
+
+/* Workspace bytes of sbe_inflight_list_keys for `limit` rows; 0 for a limit over SBE_LIST_MAX.
+ * It does not depend on the capacity of a table. */
+size_t sbe_inflight_list_workspace_size(uint32_t limit);
+
+/* The entries of `table` that pass a filter, smallest keys first.  A LIVE entry passes when the
+ * membership test in `other` holds (SBE_LIST_IN_OTHER / SBE_LIST_NOT_IN_OTHER: exactly one of them
+ * with a table `other`, none without), the answered test holds (SBE_LIST_ANSWERED /
+ * SBE_LIST_UNANSWERED, at most one) and its value is >= min_value (0: every value; 2 on a table of
+ * message ids: the ids delivered more than once).  A key is a member of `other` when a LIVE slot of
+ * its chain there holds it (an erased key is not); `other` may have another capacity and other
+ * tag_bits.  count[0] is the number of passing entries.  Rows j < min(count, limit) hold the
+ * min(count, limit) smallest passing keys ascending in std::string::compare order (bytes as
+ * unsigned, a proper prefix before the longer key: the 40 zero-padded bytes, then len); rows at or
+ * past that are not written.  limit == 0 only counts: the row arrays may be null.  A table without
+ * a valid header holds nothing: count 0 as `table`, no member as `other`.  Two launches on `stream`.
+ * SBE_EINVAL (before any launch, nothing written): a null table / out / count / workspace, a null
+ * row array with limit > 0, limit > SBE_LIST_MAX, an unknown flag bit, both bits of a pair, a
+ * membership bit without `other` or `other` without one, other == table, a table not 64-B, count /
+ * value not 8-B or len not 4-B aligned; SBE_ENOSPC: workspace too small. */
+int sbe_inflight_list_keys(const void* table, const void* other, uint32_t flags, uint64_t min_value, uint32_t limit,
+                           const sbe_key_list_out* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The latency log: caller-owned device memory that lives across calls, 64-B aligned:
+ *   +0 u64 capacity   +8 u64 count   +16 u64 dropped   +24 u32 magic       (64-B header)
+ *   +64 int64 lat[capacity], then u64 tag[capacity]
+ * sbe_latency_log_size: 64 + 16 * capacity bytes for a capacity in 1 .. 2^31, 0 for any other.
+ * A log without a valid header is full and empty: nothing is appended, a report sees count 0. */
+size_t sbe_latency_log_size(uint64_t capacity);
+
+/* Make `log` (log_bytes >= sbe_latency_log_size(capacity)) an empty log.  One launch.  SBE_EINVAL:
+ * null or misaligned log, bad capacity, log_bytes too small. */
+int sbe_latency_log_init(void* log, size_t log_bytes, uint64_t capacity, void* stream);
+
+/* Workspace bytes of sbe_latency_append for n records (8-B aligned). */
+size_t sbe_latency_append_workspace_size(uint64_t n);
+
+/* The samples of one sbe_inflight_lookup_keys call (its code / value outputs, n records): every i
+ * with code[i] == SBE_SENT_FIRST, in index order, appends at the log's cursor
+ *   lat = (int64)(now_ns - value[i]) / (int64)unit_ns     (the difference mod 2^64, then C++
+ *                                                          division: truncation toward zero)
+ *   tag = tag_base + i                                    (mod 2^64)
+ * unit_ns 1000000 is the example's duration_cast<milliseconds>.  Samples are placed by a scan over
+ * the records, so the log is a function of the call sequence.  Samples that do not fit are dropped
+ * and counted in the header's `dropped`; count never exceeds capacity.  Three launches on `stream`.
+ * SBE_EINVAL (before any launch): a null or misaligned log, n >= 2^32, and for n > 0 a null code /
+ * value / workspace, value or workspace not 8-B aligned, unit_ns outside 1 .. 2^62; SBE_ENOSPC:
+ * workspace too small.  n == 0 is SBE_OK: only log is looked at. */
+int sbe_latency_append(void* log, const uint8_t* code, const uint64_t* value, uint64_t n, uint64_t now_ns,
+                       uint64_t unit_ns, uint64_t tag_base, void* workspace, size_t workspace_bytes, void* stream);
+
+#define SBE_LAT_MAX_PCT 16u
+typedef struct sbe_latency_report_out { /* device arrays; 8-B aligned, order 4-B */
+    uint64_t* count;     /* [1] samples in the log */
+    int64_t* stats;      /* [3] sum (mod 2^64), min, max; all 0 when count == 0 */
+    int64_t* pct_value;  /* [n_pct]; 0 when count == 0 */
+    uint64_t* pct_index; /* [n_pct] the index the value was read from; 0 when count == 0 */
+    int64_t* sorted;     /* NULL, or [log capacity]: the first `count` entries written, ascending */
+    uint32_t* order;     /* NULL, or [log capacity]: order[j] = log position of sorted[j] */
+} sbe_latency_report_out;
+
+/* Workspace bytes of sbe_latency_report for a log of `capacity` samples; 0 for a bad capacity. */
+size_t sbe_latency_report_workspace_size(uint64_t capacity);
+
+/* printLatencyReport's numbers.  The samples are ordered ascending by (lat, log position): a
+ * stable sort of signed 64-bit values (the example's descending row list is `order` read from the
+ * end).  For pct[p] the index is computed in double precision on the device from the log's count,
+ * with the example's operations in its order (:322-326):
+ *   rank = (pct / 100.0) * (double)count;  idx = rank <= 0.0 ? 0 : (size_t)ceil(rank) - 1;
+ *   idx = min(idx, count - 1)
+ * which is not the textbook index: with 1000 samples p99.9 reads index 999.  The average is
+ * (double)sum / (double)count on the host, as :334.  pct is host memory, read during the call.
+ * The log is not modified.  The host cannot read the log's capacity: a workspace of
+ * sbe_latency_report_workspace_size(capacity) bytes always suffices, and a log holding more samples
+ * than workspace_bytes provides for is reported like a log without a valid header (count 0).  A
+ * memset of stats and 25 launches on `stream` (8 passes of histogram, scan, scatter; one to read
+ * the results).  SBE_EINVAL (before any launch): a null log / out / count / stats / workspace,
+ * n_pct > SBE_LAT_MAX_PCT, n_pct > 0 with a null pct / pct_value / pct_index, a pct that is not
+ * finite or outside [0, 100], a log not 64-B or an array below its alignment; SBE_ENOSPC: a
+ * workspace below sbe_latency_report_workspace_size(1). */
+int sbe_latency_report(const void* log, const double* pct, uint32_t n_pct, const sbe_latency_report_out* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ============================ Aeron fragment reassembly ============================ */
 /* Replaces LocalFragmentReassembler::onFragment (src/cluster_client.cpp:39-82) for a batch of

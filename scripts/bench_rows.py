@@ -31,6 +31,11 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
                          (message ids), note (client ids) and lookup (sent) timed as one region, the
                          nine-path extract before it timed beside it, and a one-thread std::set /
                          std::map run of the example's callback on the host
+  delivery_report        the reports read from those sets: 2 M-slot sent and received tables with 1 M sent
+                         ids, about 1 % never received and 1 % of the received never sent, and a log of
+                         1 M latencies: sbe_inflight_list_keys both ways (limit 10) and
+                         sbe_latency_report (seven percentiles, order) timed as one region, and a
+                         one-thread std::set / std::sort run of the example's reports on the host
 Rows whose buffers fit the 256 MB MALL a few times over rotate over --rotate (3) copies of their
 inputs and outputs (step k uses copy k mod R), as bench.py does, so no step finds its inputs in the
 cache a previous step left them in; config 4's 16.8 M-record batch (~6.5 GB) needs no rotation.
@@ -894,11 +899,109 @@ def row_delivery_track(steps, warmup):
     line("delivery_track", n, (ms_keys + ms_tab) * 1e-3, kernels)
 
 
+def row_delivery_report(steps, warmup):
+    """The example's three reports (examples/pubsub_reconnect_test.cpp:130-204, :276-353) read on the
+    device: 2 M-slot sent and received tables with 1 M sent "cid_<17 digits>" ids, about 1 % of them
+    never received and about 1 % of the received ids never sent, and a log of 1 M latencies.  Timed
+    as one region: sbe_inflight_list_keys sent \\ received and received \\ sent with limit 10
+    (2 launches each), sbe_latency_report with the seven reference percentiles and `order`
+    (a memset and 25 launches).  Nothing is modified, so the steps only rotate over the copies.
+    Bytes: list_keys reads 64 B x capacity of `table` and one 64-B probe line in `other` per live
+    entry that reaches the membership stage; the sort moves 16 B x count read and written per pass,
+    over 8 passes.  CPU: tests/report/report_baseline, one thread."""
+    import subprocess
+    import report_lib as RL
+    n, cap, log_cap = 1_000_000, 1 << 21, 1 << 20
+    rng = np.random.default_rng(0x5EED0FA)
+
+    def ids(prefix, count):
+        k = np.empty((count, 21), np.uint8)
+        k[:, :4] = np.frombuffer(prefix, np.uint8)
+        k[:, 4:] = rng.integers(0, 10, (count, 17)) + ord("0")
+        return k
+    sent = ids(b"cid_", n)
+    assert np.unique(sent.view("S21")).size == n
+    got = rng.random(n) >= 0.01
+    extra = ids(b"xid_", n // 100)
+    recv = np.concatenate([sent[got], extra])
+    lat_ns = rng.integers(0, 2_000_000_000, n).astype(np.uint64)  # send times around now: -1000 .. 1000 ms
+    now = 1_000_000_000
+
+    def table(keys):
+        t = sbecodec.Inflight(cap, "cuda")
+        m = keys.shape[0]
+        st = t.remember(dev(keys.reshape(-1), torch.uint8), dev((21 * np.arange(m)).astype(np.int32), torch.int32),
+                        dev(np.full(m, 21, np.int32), torch.int32), ts_default=1000)
+        assert int((st != sbecodec.INF_INSERTED).sum()) == 0
+        return t
+    pct = sbecodec.REPORT_PERCENTILES
+
+    def make(k):
+        ts, tr = table(sent), table(recv)
+        log = sbecodec.LatencyLog(log_cap, "cuda")
+        log.append(sbecodec.KeyLookups(torch.full((n,), sbecodec.SENT_FIRST, dtype=torch.uint8, device="cuda"),
+                                       dev(lat_ns, torch.int64), None), now, 1_000_000)
+        outs = (ts.list_keys(tr, sbecodec.LIST_NOT_IN_OTHER, limit=10), tr.list_keys(ts, sbecodec.LIST_NOT_IN_OTHER, limit=10),
+                log.report(pct, want_order=True))
+        return ts, tr, log, outs
+    R = Rot(make)
+    torch.cuda.synchronize()
+    # the model: std::set order is the order of the sorted byte strings
+    missing = sorted(bytes(r) for r in sent[~got])
+    extras = sorted(set(bytes(r) for r in extra))
+    m0, e0, r0 = R.sets[0][3]
+    assert int(m0.numpy()["count"][0]) == len(missing) and [r[0] for r in m0.rows()] == missing[:10]
+    assert int(e0.numpy()["count"][0]) == len(extras) and [r[0] for r in e0.rows()] == extras[:10]
+    d = now - lat_ns.astype(np.int64)
+    lats = np.where(d >= 0, d // 1_000_000, -((-d) // 1_000_000))  # C++ division truncates toward zero
+    order = np.argsort(lats, kind="stable")
+    rep = r0.numpy()
+    assert int(rep["count"][0]) == n and np.array_equal(rep["sorted"][:n], lats[order]) and np.array_equal(rep["order"][:n], order)
+    assert list(rep["pct_index"]) == [RL.percentile_index(p, n) for p in pct]
+    assert list(rep["pct_value"]) == [int(lats[order][RL.percentile_index(p, n)]) for p in pct]
+    assert list(rep["stats"]) == [int(lats.sum()), int(lats.min()), int(lats.max())]
+
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(steps)]
+
+    def step(e):
+        ts, tr, log, (om, oe, orp) = R.next()
+        if e:
+            e[0].record()
+        ts.list_keys(tr, sbecodec.LIST_NOT_IN_OTHER, limit=10, out=om)
+        tr.list_keys(ts, sbecodec.LIST_NOT_IN_OTHER, limit=10, out=oe)
+        if e:
+            e[1].record()
+        log.report(pct, want_order=True, out=orp)
+        if e:
+            e[2].record()
+    for _ in range(warmup):
+        step(None)
+    torch.cuda.synchronize()
+    for e in ev:
+        step(e)
+    torch.cuda.synchronize()
+    t = np.array([[e[j].elapsed_time(e[j + 1]) for j in range(2)] for e in ev])
+    ms_list, ms_rep = (float(v) for v in np.median(t, axis=0))
+    kernels = {"sbe_inflight_list_keys x2 (4 launches)": (ms_list, 2 * 64 * cap + 64 * (n + recv.shape[0])),
+               "sbe_latency_report (memset + 25 launches)": (ms_rep, 2 * 16 * 8 * n)}
+    extra_line = {"row": "delivery_report", "missing": len(missing), "extra": len(extras), "samples": n, "capacity": cap,
+                  "ms_min": {"lists": float(t[:, 0].min()), "report": float(t[:, 1].min())}}
+    if not NO_CPU:
+        d = os.path.join(ROOT, "tests", "report")
+        subprocess.run(["make", "-s", "-C", d, "report_baseline"], check=True)
+        cpu = json.loads(subprocess.run([os.path.join(d, "report_baseline"), str(n)], check=True, capture_output=True,
+                                        text=True).stdout)
+        extra_line["cpu_set_sort_one_thread"] = cpu
+        extra_line["cpu_over_device"] = cpu["report_ms"] / (ms_list + ms_rep)
+    print(json.dumps(extra_line), flush=True)
+    line("delivery_report", n, (ms_list + ms_rep) * 1e-3, kernels)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,commit_emit,commit_fallback,ack_correlate,delivery_track")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,commit_emit,commit_fallback,ack_correlate,delivery_track,delivery_report")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -937,6 +1040,8 @@ def main():
             row_ack_correlate(args.steps, args.warmup)
         elif r == "delivery_track":
             row_delivery_track(args.steps, args.warmup)
+        elif r == "delivery_report":
+            row_delivery_report(args.steps, args.warmup)
         elif r.startswith("lite"):
             row_lite(int(r[4:]), args.steps, args.warmup)
         torch.cuda.empty_cache()
