@@ -3674,7 +3674,8 @@ __global__ __launch_bounds__(256) void frag_copy(FragArgs a) {
 // overlapping the chunk before it with the same bytes; a view under 16 bytes is written bytewise
 // from one 16-byte load that stays inside the record), then the wave stores the window with 16-byte
 // coalesced nontemporal stores and moves it on to the first record not yet written.  A record
-// larger than the window is copied by its own lane straight to the arena.  Measured (1 M fixed-256
+// larger than the window is copied by its own lane straight to the arena, and a window round ends
+// before the next such record (its stores cover its whole range).  Measured (1 M fixed-256
 // records, all three launches; profiles/r06_ab_mat*.log): one thread a record copying straight to
 // the arena 0.823 ms (every store instruction wrote 64 scattered 16-byte pieces); the LDS window
 // with one dependent load a chunk 0.184 ms; batches of 1 / 4 / 8 chunk loads 0.221 / 0.169 / 0.170
@@ -3924,15 +3925,24 @@ __device__ __forceinline__ void mat_tile(const MatArgs& a, uint64_t t, const Mat
     const uint8_t* rec = a.in + r0;
     const uint64_t rl = r1 - r0;
     bool done = fit == o;
-    if (!done && fit - o > (uint64_t)(kMatWin - 16)) {  // larger than any window: straight to the arena
+    const bool direct = !done && fit - o > (uint64_t)(kMatWin - 16);
+    if (direct) {  // larger than any window: straight to the arena
         mat_views_direct(a.arena + o, rec, rl, at, L, O, k_end, fit);
         done = true;
     }
+    // A round stores the whole range [start, cend) from the window, so it must end before the next
+    // direct-copied record: that range of the window is never staged.  Tiles without one (the
+    // ballot) skip the reduction.
+    const bool any_direct = __ballot(direct) != 0;
     uint64_t start = mat_wave_min(done ? ~0ull : o);
     while (start != ~0ull) {  // uniform
         const uint64_t wbase = start - (uint64_t)((reinterpret_cast<uintptr_t>(a.arena) + start) & 15u);
+        // the first direct-copied record after start (the record at start ends at or before it: it
+        // sits in an earlier lane and has bytes, so every round still finishes that record)
+        uint64_t bound = ~0ull;
+        if (any_direct) bound = mat_wave_min(direct && o >= start ? o : ~0ull);
         uint64_t my_end = 0;
-        if (!done && fit - wbase <= (uint64_t)kMatWin) {
+        if (!done && fit - wbase <= (uint64_t)kMatWin && fit <= bound) {
             mat_views_lds((mat_lds8*)win + (o - wbase), rec, rl, at, L, O, k_end);
             done = true;
             my_end = fit;
@@ -4966,6 +4976,9 @@ int sbe_materialize_views(const uint8_t* in, const uint64_t* rec_off, uint64_t n
     if (n == 0) return record_hip(hipMemsetAsync(arena_off, 0, 8, s));
     if (!in || !rec_off || !dec || !dec->status || !dec->view_off || !dec->view_len || !workspace) return SBE_EINVAL;
     if (!arena && arena_capacity) return SBE_EINVAL;
+    if (misaligned(rec_off, 7) || misaligned(arena_off, 7) || misaligned(dec->view_off, 3) ||
+        misaligned(dec->view_len, 3))
+        return SBE_EINVAL;
     if (workspace_bytes < sbe_materialize_workspace_size(n)) return SBE_ENOSPC;
     const uint64_t nb = (n + kMatBlk - 1) / kMatBlk;      // mat_sums blocks
     const uint64_t nt = (n + kMatTile - 1) / kMatTile;    // copy waves

@@ -353,8 +353,11 @@ int sbe_eval_sequence_numbers(const uint8_t* in, const uint64_t* rec_off, uint64
  * A view that would end past arena_capacity is not written (arena_off still holds the full
  * layout, so the caller can size the arena from arena_off[5 n] and rerun); nothing is written past
  * arena_capacity: the views written are a prefix of the layout, and the arena is untouched from
- * the end of the last view written.  Alignment: rec_off / arena_off 8 B, views 4 B; in and arena
- * need none.  Workspace: sbe_materialize_workspace_size(n) bytes (16-B aligned). */
+ * the end of the last view written.  dec->status must be non-null and is not read: every record is
+ * copied by the view_len its decode left, whatever its status (a record the decode rejected has
+ * the lengths that decode wrote for it).  Alignment: rec_off / arena_off 8 B, view_off / view_len
+ * 4 B (SBE_EINVAL otherwise, before any launch); in and arena need none.  Workspace:
+ * sbe_materialize_workspace_size(n) bytes (16-B aligned). */
 size_t sbe_materialize_workspace_size(uint64_t n);
 int sbe_materialize_views(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
                           uint8_t* arena, uint64_t arena_capacity, uint64_t* arena_off, void* workspace,
