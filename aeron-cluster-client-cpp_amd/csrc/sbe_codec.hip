@@ -4373,6 +4373,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 #include "json_paths.hpp"
 #include "delivery_keys.hpp"
 #include "delivery_report.hpp"
+#include "order_select.hpp"
 
 }  // namespace
 
@@ -5274,6 +5275,26 @@ int sbe_delivery_keys(const uint64_t* rec_off, uint64_t n, const sbe_decoded* de
              ids->root_kind, ids->kind,  ids->off,      ids->len,      out->msg_pos,   out->msg_len,  out->coid_pos,
              out->coid_len, out->coid_kind, out->oid_pos, out->oid_len, out->oid_kind, out->selected, out->totals};
     hipLaunchKernelGGL(sbe_delivery_keys_kernel, dim3((uint32_t)((n + kDkBlk - 1) / kDkBlk)), dim3(kDkBlk), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+uint32_t sbe_order_select_window(void) { return kOsWin; }
+
+int sbe_order_select(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                     const sbe_select_out* out, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!out || !out->totals || misaligned(out->totals, 7) || n >= (1ull << 32)) return SBE_EINVAL;
+    if (n && (!in || !rec_off || !dec || !dec->status || !dec->flags || !dec->hdr || !dec->view_off || !dec->view_len ||
+              !out->pred))
+        return SBE_EINVAL;
+    if (n && (misaligned(rec_off, 7) || misaligned(dec->hdr, 1) || misaligned(dec->view_off, 3) ||
+              misaligned(dec->view_len, 3)))
+        return SBE_EINVAL;
+    if (const int rc = record_hip(hipMemsetAsync(out->totals, 0, 16, s))) return rc;
+    if (n == 0) return SBE_OK;
+    OsArgs a{in,           rec_off,       n,         dec->status, dec->flags,       dec->hdr,
+             dec->view_off, dec->view_len, out->pred, out->select, out->topic_class, out->totals};
+    hipLaunchKernelGGL(sbe_order_select_kernel, dim3((uint32_t)((n + kTile - 1) / kTile)), dim3(kWave), 0, s, a);
     return record_hip(hipGetLastError());
 }
 

@@ -3352,10 +3352,12 @@ JsonPath::JsonPath(const std::string& dotted) {
 
 struct JsonExtractAccess {
     // One launch over staged records.  d: the decode descriptors (null: bare documents, view 0);
-    // piece(i): record i's bytes; out.base_ is the caller's to fill.
+    // piece(i): record i's bytes; out.base_ is the caller's to fill.  order_select (with d, and no
+    // select of the caller's): the mask is sbe_order_select's, computed on the device in front of
+    // the extract, on the same stream.
     template <class Piece>
     static void run(size_t n, const Descriptors* d, int view, const uint8_t* select, const std::vector<JsonPath>& paths,
-                    const Piece& piece, JsonFields& out) {
+                    const Piece& piece, JsonFields& out, bool order_select = false) {
         std::vector<uint8_t> depth, names;
         std::vector<uint32_t> name_off{0};
         for (const JsonPath& p : paths) {
@@ -3386,8 +3388,12 @@ struct JsonExtractAccess {
         for (size_t i = 0; i < n; ++i) start[i + 1] = start[i] + piece(i).size();
         const size_t bytes = (size_t)start[n];
         const size_t o_st = al16((n + 1) * 8), o_fl = o_st + (d ? al16(n) : 0), o_vo = o_fl + (d ? al16(n) : 0),
-                     o_vl = o_vo + (d ? al16(20 * n) : 0), o_sel = o_vl + (d ? al16(20 * n) : 0),
-                     o_data = o_sel + (select ? al16(n) : 0), stage = o_data + bytes + 16;
+                     o_vl = o_vo + (d ? al16(20 * n) : 0), o_hd = o_vl + (d ? al16(20 * n) : 0),
+                     o_sel = o_hd + (order_select ? al16(8 * n) : 0), o_data = o_sel + (select ? al16(n) : 0),
+                     stage = o_data + bytes + 16;
+        // behind the staged bytes, written by the device only: the mask, pred and totals of sbe_order_select
+        const size_t o_dsel = al16(stage), o_pred = o_dsel + al16(n), o_tot = o_pred + al16(n),
+                     dev_bytes = order_select ? o_tot + 16 : stage;
         Ctx& c = ctx();
         Pipeline::Slot& s = c.pipe.slot[0];  // serial use of the pipeline's first slot (idle between calls)
         hipStream_t stream = c.batch_stream();
@@ -3401,25 +3407,35 @@ struct JsonExtractAccess {
                     hp[o_fl + i] = d->flags(i);
                     std::memcpy(hp + o_vo + 20 * i, d->off(i), 20);
                     std::memcpy(hp + o_vl + 20 * i, d->len(i), 20);
+                    if (order_select) std::memcpy(hp + o_hd + 8 * i, d->hdr(i), 8);
                 }
                 if (select) hp[o_sel + i] = select[i];
                 const std::string_view r = piece(i);
                 if (!r.empty()) std::memcpy(hp + o_data + start[i], r.data(), r.size());
             }
         });
-        s.d_in.need(stage);
+        s.d_in.need(dev_bytes);
         const size_t p_root = al16(n), p_kind = p_root + al16(n), p_off = p_kind + al16(n * P), p_len = p_off + al16(4 * n * P),
                      outb = p_len + al16(4 * n * P);
         s.d_out.need(outb);
         hip_check(hipMemcpyAsync(s.d_in.p, hp, stage, hipMemcpyHostToDevice, stream), "H2D");
         uint8_t* di = s.d_in.b();
         uint8_t* dq = s.d_out.b();
-        const sbe_decoded dec{di + o_st, di + o_fl, nullptr, nullptr, reinterpret_cast<uint32_t*>(di + o_vo),
-                              reinterpret_cast<uint32_t*>(di + o_vl), nullptr};
+        const sbe_decoded dec{di + o_st, di + o_fl, order_select ? reinterpret_cast<uint16_t*>(di + o_hd) : nullptr, nullptr,
+                              reinterpret_cast<uint32_t*>(di + o_vo), reinterpret_cast<uint32_t*>(di + o_vl), nullptr};
         sbe_json_out res{dq, dq + p_root, dq + p_kind, reinterpret_cast<uint32_t*>(dq + p_off),
                          reinterpret_cast<uint32_t*>(dq + p_len)};
+        const uint8_t* d_select = select ? di + o_sel : nullptr;
+        if (order_select) {
+            const sbe_select_out so{di + o_pred, di + o_dsel, nullptr, reinterpret_cast<uint64_t*>(di + o_tot)};
+            if (sbe_order_select(di + o_data, reinterpret_cast<const uint64_t*>(di), n, &dec, &so, stream) != SBE_OK) {
+                c.abort_all();
+                fail("sbe_order_select");
+            }
+            d_select = di + o_dsel;
+        }
         const int rc = sbe_json_extract_batch(di + o_data, reinterpret_cast<const uint64_t*>(di), n, d ? &dec : nullptr,
-                                              (uint32_t)view, select ? di + o_sel : nullptr, &ps, &res, nullptr, 0, stream);
+                                              (uint32_t)view, d_select, &ps, &res, nullptr, 0, stream);
         if (rc == SBE_EINVAL) {
             hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
             throw std::invalid_argument("extract: bad path table or view");
@@ -3439,6 +3455,20 @@ struct JsonExtractAccess {
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
     }
     static std::vector<const char*>& base(JsonFields& f) { return f.base_; }
+    // batch.extract(paths, 3, mask) with sbe_order_select's mask, which stays on the device
+    static JsonFields order_fields(const ParsedBatch& batch, const std::vector<JsonPath>& paths) {
+        JsonFields f;
+        run(
+            batch.n_, batch.desc_.get(), 3, nullptr, paths,
+            [&](size_t i) {
+                return std::string_view(reinterpret_cast<const char*>(batch.data_ + batch.rec_off_[i]),
+                                        (size_t)(batch.rec_off_[i + 1] - batch.rec_off_[i]));
+            },
+            f, true);
+        f.base_.resize(batch.n_);
+        for (size_t i = 0; i < batch.n_; ++i) f.base_[i] = reinterpret_cast<const char*>(batch.data_ + batch.rec_off_[i]);
+        return f;
+    }
 };
 
 std::string_view JsonFields::token(std::size_t i, std::size_t p) const {
@@ -3517,6 +3547,71 @@ JsonFields ParsedBatch::extract(const std::vector<JsonPath>& paths, int view, co
     return f;
 }
 
+TopicClass classify_topic(std::string_view topic) {  // include/aeron_cluster/topic_router.hpp
+    if (topic == "orders" || topic == "order_request_topic") return TopicClass::Orders;
+    if (topic == "_subscriptions" || topic == "_ack" || topic == "_control" || topic == "_internal")
+        return TopicClass::Control;
+    return TopicClass::Unknown;
+}
+
+TopicClass MessageKinds::topic_class(std::size_t i) const {
+    return class_[i] == SBE_TC_ORDERS ? TopicClass::Orders : class_[i] == SBE_TC_CONTROL ? TopicClass::Control : TopicClass::Unknown;
+}
+
+MessageKinds ParsedBatch::order_select() const {
+    MessageKinds k;
+    const size_t n = n_;
+    k.pred_.assign(n, 0);
+    k.select_.assign(n, 0);
+    k.class_.assign(n, SBE_TC_UNKNOWN);
+    if (!n) return k;
+    const Descriptors* d = desc_.get();
+    const uint64_t base0 = rec_off_[0], bytes = rec_off_[n] - base0;
+    // staged as extract stages a batch: rec_off rebased to 0 | status | flags | hdr | view_off |
+    // view_len | the records; then, written by the device only: pred | select | class | totals
+    const size_t o_st = al16((n + 1) * 8), o_fl = o_st + al16(n), o_hd = o_fl + al16(n), o_vo = o_hd + al16(8 * n),
+                 o_vl = o_vo + al16(20 * n), o_data = o_vl + al16(20 * n), stage = o_data + bytes + 16;
+    const size_t r_pred = 0, r_sel = al16(n), r_cls = r_sel + al16(n), r_tot = r_cls + al16(n), outb = r_tot + 16;
+    Ctx& c = ctx();
+    Pipeline::Slot& s = c.pipe.slot[0];  // serial use of the pipeline's first slot (idle between calls)
+    hipStream_t stream = c.batch_stream();
+    s.pin.need(stage);
+    uint8_t* hp = s.pin.b();
+    uint64_t* ro = reinterpret_cast<uint64_t*>(hp);
+    for (size_t i = 0; i <= n; ++i) ro[i] = rec_off_[i] - base0;
+    for_ranges(n, 4096, [&](size_t x, size_t y) {
+        for (size_t i = x; i < y; ++i) {
+            hp[o_st + i] = d->status(i);
+            hp[o_fl + i] = d->flags(i);
+            std::memcpy(hp + o_hd + 8 * i, d->hdr(i), 8);
+            std::memcpy(hp + o_vo + 20 * i, d->off(i), 20);
+            std::memcpy(hp + o_vl + 20 * i, d->len(i), 20);
+        }
+    });
+    if (bytes) std::memcpy(hp + o_data, data_ + base0, bytes);
+    s.d_in.need(stage);
+    s.d_out.need(outb);
+    hip_check(hipMemcpyAsync(s.d_in.p, hp, stage, hipMemcpyHostToDevice, stream), "H2D");
+    uint8_t* di = s.d_in.b();
+    uint8_t* dq = s.d_out.b();
+    const sbe_decoded dec{di + o_st, di + o_fl, reinterpret_cast<uint16_t*>(di + o_hd), nullptr,
+                          reinterpret_cast<uint32_t*>(di + o_vo), reinterpret_cast<uint32_t*>(di + o_vl), nullptr};
+    const sbe_select_out so{dq + r_pred, dq + r_sel, dq + r_cls, reinterpret_cast<uint64_t*>(dq + r_tot)};
+    if (sbe_order_select(di + o_data, reinterpret_cast<const uint64_t*>(di), n, &dec, &so, stream) != SBE_OK) {
+        c.abort_all();
+        fail("sbe_order_select");
+    }
+    auto back = [&](void* dst, size_t off, size_t len) {
+        hip_check(hipMemcpyAsync(dst, dq + off, len, hipMemcpyDeviceToHost, stream), "D2H");
+    };
+    back(k.pred_.data(), r_pred, n);
+    back(k.select_.data(), r_sel, n);
+    back(k.class_.data(), r_cls, n);
+    back(k.totals_, r_tot, 16);
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    return k;
+}
+
 JsonFields extract_json_documents(const std::vector<std::string>& docs, const std::vector<JsonPath>& paths) {
     JsonFields f;
     JsonExtractAccess::run(docs.size(), nullptr, 0, nullptr, paths, [&](size_t i) { return std::string_view(docs[i]); }, f);
@@ -3563,16 +3658,7 @@ bool order_callback_looks(const ParseResult& r) {  // :578-579
 
 std::vector<OrderIds> extract_order_ids(const ParsedBatch& batch) {
     const size_t n = batch.size();
-    std::vector<uint8_t> select(n, 0);
-    for_ranges(n, 1024, [&](size_t x, size_t y) {
-        ParseResult r;
-        for (size_t i = x; i < y; ++i) {
-            if (batch.status(i) != SBE_ST_TM) continue;
-            batch.result_into(i, r);
-            select[i] = order_callback_looks(r) ? 1 : 0;
-        }
-    });
-    const JsonFields f = batch.extract(order_id_paths(), 3, select.data());
+    const JsonFields f = JsonExtractAccess::order_fields(batch, order_id_paths());  // :578-579 on the device
     std::vector<OrderIds> out(n);
     for_ranges(n, 1024, [&](size_t x, size_t y) {
         for (size_t i = x; i < y; ++i) out[i] = order_ids_of(f, i);
@@ -4024,25 +4110,21 @@ std::vector<Delivery> DeliveryTracker::on_batch(const ParsedBatch& batch, std::u
     const uint64_t base0 = batch.rec_off_[0], bytes = batch.rec_off_[n] - base0;
     const char* host = reinterpret_cast<const char*>(batch.data_ + base0);
     constexpr size_t P = SBE_DLV_PATHS;
-    // staged: rec_off rebased to 0 [n + 1] | status | flags | view_off | view_len | select | the
+    // staged: rec_off rebased to 0 [n + 1] | status | flags | view_off | view_len | hdr | the
     // records | room for the decoded forms of escaped ids (never longer than their tokens)
     const size_t o_st = al64(8 * (n + 1)), o_fl = o_st + al64(n), o_vo = o_fl + al64(n), o_vl = o_vo + al64(20 * n),
-                 o_sel = o_vl + al64(20 * n), o_data = o_sel + al64(n), total_in = o_data + 2 * bytes + 16;
+                 o_hd = o_vl + al64(20 * n), o_data = o_hd + al64(8 * n), total_in = o_data + 2 * bytes + 16;
     m.stage.resize(o_data + bytes);
     uint8_t* hp = m.stage.data();
     uint64_t* ro = reinterpret_cast<uint64_t*>(hp);
     for (size_t i = 0; i <= n; ++i) ro[i] = batch.rec_off_[i] - base0;
-    for_ranges(n, 1024, [&](size_t x, size_t y) {
-        ParseResult r;
+    for_ranges(n, 4096, [&](size_t x, size_t y) {
         for (size_t i = x; i < y; ++i) {
             hp[o_st + i] = d->status(i);
             hp[o_fl + i] = d->flags(i);
             std::memcpy(hp + o_vo + 20 * i, d->off(i), 20);
             std::memcpy(hp + o_vl + 20 * i, d->len(i), 20);
-            hp[o_sel + i] = 0;
-            if (d->status(i) != SBE_ST_TM) continue;
-            batch.result_into(i, r);
-            hp[o_sel + i] = order_callback_looks(r) ? 1 : 0;
+            std::memcpy(hp + o_hd + 8 * i, d->hdr(i), 8);
         }
     });
     if (bytes) std::memcpy(hp + o_data, host, bytes);
@@ -4064,6 +4146,9 @@ std::vector<Delivery> DeliveryTracker::on_batch(const ParsedBatch& batch, std::u
     const size_t k_okind = q; q = al64(q + n);
     const size_t k_sel = q; q = al64(q + n);
     const size_t k_tot = q; q = al64(q + 16);
+    const size_t s_sel = q; q = al64(q + n);  // sbe_order_select: the callback's outer if (:578-579), pred, totals
+    const size_t s_pred = q; q = al64(q + n);
+    const size_t s_tot = q; q = al64(q + 16);
     const size_t o_res = q;
     m.in.need(total_in);
     m.out.need(o_res + L.total);
@@ -4071,9 +4156,11 @@ std::vector<Delivery> DeliveryTracker::on_batch(const ParsedBatch& batch, std::u
     uint8_t* di = m.in.b();
     uint8_t* dq = m.out.b();
     const uint64_t* d_ro = reinterpret_cast<const uint64_t*>(di);
-    const sbe_decoded dec{di + o_st, di + o_fl, nullptr, nullptr, reinterpret_cast<uint32_t*>(di + o_vo),
-                          reinterpret_cast<uint32_t*>(di + o_vl), nullptr};
+    const sbe_decoded dec{di + o_st, di + o_fl, reinterpret_cast<uint16_t*>(di + o_hd), nullptr,
+                          reinterpret_cast<uint32_t*>(di + o_vo), reinterpret_cast<uint32_t*>(di + o_vl), nullptr};
     {
+        const sbe_select_out so{dq + s_pred, dq + s_sel, nullptr, reinterpret_cast<uint64_t*>(dq + s_tot)};
+        if (sbe_order_select(di + o_data, d_ro, n, &dec, &so, m.stream) != SBE_OK) fail("sbe_order_select");
         std::vector<uint8_t> depth, names;
         std::vector<uint32_t> name_off{0};
         for (const JsonPath& p : order_id_paths()) {
@@ -4086,14 +4173,14 @@ std::vector<Delivery> DeliveryTracker::on_batch(const ParsedBatch& batch, std::u
         const sbe_json_paths ps{(uint32_t)depth.size(), depth.data(), names.data(), name_off.data()};
         sbe_json_out jo{dq + j_doc, dq + j_root, dq + j_kind, reinterpret_cast<uint32_t*>(dq + j_off),
                         reinterpret_cast<uint32_t*>(dq + j_len)};
-        if (sbe_json_extract_batch(di + o_data, d_ro, n, &dec, 3, di + o_sel, &ps, &jo, nullptr, 0, m.stream) != SBE_OK)
+        if (sbe_json_extract_batch(di + o_data, d_ro, n, &dec, 3, dq + s_sel, &ps, &jo, nullptr, 0, m.stream) != SBE_OK)
             fail("sbe_json_extract_batch");
         const sbe_delivery_key_out ko{reinterpret_cast<uint64_t*>(dq + k_mpos), reinterpret_cast<uint32_t*>(dq + k_mlen),
                                       reinterpret_cast<uint64_t*>(dq + k_cpos), reinterpret_cast<uint32_t*>(dq + k_clen),
                                       dq + k_ckind,
                                       reinterpret_cast<uint64_t*>(dq + k_opos), reinterpret_cast<uint32_t*>(dq + k_olen),
                                       dq + k_okind, dq + k_sel, reinterpret_cast<uint64_t*>(dq + k_tot)};
-        if (sbe_delivery_keys(d_ro, n, &dec, di + o_sel, &jo, &ko, m.stream) != SBE_OK) fail("sbe_delivery_keys");
+        if (sbe_delivery_keys(d_ro, n, &dec, dq + s_sel, &jo, &ko, m.stream) != SBE_OK) fail("sbe_delivery_keys");
     }
     std::vector<uint64_t> mpos(n), cpos(n), opos(n);
     std::vector<uint32_t> mlen(n), clen(n), olen(n);

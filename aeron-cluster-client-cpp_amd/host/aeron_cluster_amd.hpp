@@ -326,6 +326,30 @@ struct OrderIds {
 std::vector<OrderIds> extract_order_ids(const ParsedBatch& batch);
 OrderIds extract_order_ids(const ParseResult& result);
 
+// include/aeron_cluster/topic_router.hpp: "orders" and "order_request_topic" are Orders;
+// "_subscriptions", "_ack", "_control" and "_internal" are Control.
+enum class TopicClass { Orders, Control, Unknown };
+TopicClass classify_topic(std::string_view topic);
+
+// ParsedBatch::order_select's result (sbe_order_select): what the ParseResult predicates say of
+// every record, without building a ParseResult.
+class MessageKinds {
+public:
+    std::size_t size() const { return pred_.size(); }
+    // SBE_PR_* bits: result(i).is_session_event() / is_topic_message() / is_acknowledgment() / is_order_message()
+    std::uint8_t pred(std::size_t i) const { return pred_[i]; }
+    // the subscriber's test (examples/pubsub_reconnect_test.cpp:578-579) on a TopicMessage record
+    bool selected(std::size_t i) const { return select_[i] != 0; }
+    TopicClass topic_class(std::size_t i) const;  // classify_topic of a TopicMessage's topic; Unknown for other records
+    std::uint64_t selected_count() const { return totals_[0]; }
+    std::uint64_t order_count() const { return totals_[1]; }  // records with is_order_message()
+
+private:
+    friend class ParsedBatch;
+    std::vector<std::uint8_t> pred_, select_, class_;
+    std::uint64_t totals_[2] = {0, 0};
+};
+
 class MessageParser {
 public:
     // src/sbe_encoder.cpp:513-551 (never throws; success = false + error_message)
@@ -387,9 +411,13 @@ public:
     // on the device as Json::parseFromStream with builder defaults reads them
     // (sbe_json_extract_batch); select: null, or n bytes, 0 skips the record.
     JsonFields extract(const std::vector<JsonPath>& paths, int view = 3, const std::uint8_t* select = nullptr) const;
+    // The ParseResult predicates of every record, the subscriber's order test and the topic class,
+    // computed on the device from the descriptors and the record bytes (sbe_order_select).
+    MessageKinds order_select() const;
 
 private:
     friend class MessageParser;
+    friend struct JsonExtractAccess;
     friend class AutoCommitter;
     friend class DeliveryTracker;
     std::shared_ptr<const detail::Descriptors> desc_;  // host copy of the device descriptors

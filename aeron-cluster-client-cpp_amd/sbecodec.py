@@ -142,6 +142,10 @@ class _DeliveryKeyOut(ctypes.Structure):
                                                "oid_len", "oid_kind", "selected", "totals")]
 
 
+class _SelectOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("pred", "select", "topic_class", "totals")]
+
+
 class _KeyListOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("count", "key", "len", "value", "answered")]
 
@@ -269,6 +273,11 @@ def _load():
     lib.sbe_delivery_keys.restype = ctypes.c_int
     lib.sbe_delivery_keys.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_Decoded), ctypes.c_void_p,
                                       ctypes.POINTER(_JsonOut), ctypes.POINTER(_DeliveryKeyOut), ctypes.c_void_p]
+    lib.sbe_order_select.restype = ctypes.c_int
+    lib.sbe_order_select.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(_Decoded),
+                                     ctypes.POINTER(_SelectOut), ctypes.c_void_p]
+    lib.sbe_order_select_window.restype = ctypes.c_uint32
+    lib.sbe_order_select_window.argtypes = []
     lib.sbe_inflight_list_workspace_size.restype = ctypes.c_size_t
     lib.sbe_inflight_list_workspace_size.argtypes = [ctypes.c_uint32]
     lib.sbe_inflight_list_keys.restype = ctypes.c_int
@@ -1097,6 +1106,60 @@ def delivery_keys(rec_off, dec: Decoded, ids: JsonFields, select=None, out: Deli
     _check(rc, "sbe_delivery_keys")
     if n < out.selected.numel():
         out = DeliveryKeys(*(getattr(out, k) if k == "totals" else getattr(out, k)[:n] for k, _ in _DELIVERY_KEYS))
+    return out
+
+
+# sbe_order_select: pred bits and topic classes
+PR_SESSION_EVENT, PR_TOPIC_MESSAGE, PR_ACKNOWLEDGMENT, PR_ORDER_MESSAGE = 1, 2, 4, 8
+TC_UNKNOWN, TC_ORDERS, TC_CONTROL = 0, 1, 2
+
+
+@dataclass
+class MessageKinds:
+    pred: torch.Tensor                # uint8 [n]  PR_* bits
+    select: torch.Tensor | None       # uint8 [n]  1: an ST_TM record with PR_ORDER_MESSAGE
+    topic_class: torch.Tensor | None  # uint8 [n]  TC_*
+    totals: torch.Tensor              # int64 [2]  (u64) selected records, records with PR_ORDER_MESSAGE
+
+    def numpy(self):
+        import numpy as np
+        d = {"pred": self.pred.cpu().numpy(), "totals": self.totals.cpu().numpy().view(np.uint64)}
+        for k in ("select", "topic_class"):
+            if getattr(self, k) is not None:
+                d[k] = getattr(self, k).cpu().numpy()
+        return d
+
+
+def order_select_window() -> int:
+    """Bytes of the LDS window sbe_order_select searches a tile's payloads in."""
+    return int(lib().sbe_order_select_window())
+
+
+def order_select(buf, rec_off, dec: Decoded, want_select=True, want_class=True, out: MessageKinds | None = None,
+                 stream=None) -> MessageKinds:
+    """The ParseResult predicates (is_session_event / is_topic_message / is_acknowledgment /
+    is_order_message) of every record of a parse-mode decode_batch on the same buf / rec_off, the
+    mask the subscriber's callback starts with (examples/pubsub_reconnect_test.cpp:578-579; pass it
+    as `select` to extract_json and delivery_keys) and classify_topic of the record's topic."""
+    buf = _dev(buf, torch.uint8, "buf")
+    rec_off = _dev(rec_off, torch.int64, "rec_off")
+    n = int(rec_off.numel()) - 1
+    dev = rec_off.device
+    if min(dec.status.numel(), dec.flags.numel()) < n or dec.hdr.numel() < 4 * n or \
+            min(dec.view_off.numel(), dec.view_len.numel()) < 5 * n:
+        raise SbeError("order_select: dec holds fewer than n records")
+    if out is None:
+        def arr(want):
+            return torch.empty(max(n, 1), dtype=torch.uint8, device=dev) if want else None
+        out = MessageKinds(arr(True), arr(want_select), arr(want_class), torch.empty(2, dtype=torch.int64, device=dev))
+    d = _Decoded(*(getattr(dec, f).data_ptr() for f in ("status", "flags", "hdr", "ts", "view_off", "view_len")))
+    o = _SelectOut(out.pred.data_ptr(), None if out.select is None else out.select.data_ptr(),
+                   None if out.topic_class is None else out.topic_class.data_ptr(), out.totals.data_ptr())
+    rc = lib().sbe_order_select(_ptr(buf), _ptr(rec_off), n, ctypes.byref(d), ctypes.byref(o), _stream(stream))
+    _check(rc, "sbe_order_select")
+    if n < out.pred.numel():
+        out = MessageKinds(out.pred[:n], None if out.select is None else out.select[:n],
+                           None if out.topic_class is None else out.topic_class[:n], out.totals)
     return out
 
 

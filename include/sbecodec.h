@@ -82,6 +82,10 @@
  *                                  (sbe_inflight_reset_values: clear_duplicate_tracking, :70-73)
  * sbe_delivery_keys()             the three keys of those lookups per record: message_id and the
  *                                  client_order_id / order_id the callback picks, :592-619
+ * sbe_order_select()              the test in front of them, :578-579: ParseResult::is_order_message /
+ *                                  is_topic_message / is_session_event / is_acknowledgment
+ *                                  include/aeron_cluster/sbe_messages.hpp:332-406 per record, and
+ *                                  classify_topic include/aeron_cluster/topic_router.hpp
  * sbe_inflight_list_keys()        printMessageComparison examples/pubsub_reconnect_test.cpp:130-204 and
  *                                  printClientOrderAudit :206-274: the ids sent and never received, or
  *                                  received and never sent, the first ones in std::set order; with a
@@ -833,6 +837,54 @@ typedef struct sbe_delivery_key_out { /* device arrays of n elements; u64 8-B, u
  * n >= 2^32, an array below its alignment. */
 int sbe_delivery_keys(const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec, const uint8_t* select,
                       const sbe_json_out* ids, const sbe_delivery_key_out* out, void* stream);
+
+/* ============================== message kinds, order select ============================== */
+/* The test in front of all of the above, the first line of the callback (:578-579):
+ *   result.is_order_message() || (result.is_topic_message() && result.message_type == "CREATE_ORDER")
+ * i.e. the ParseResult predicates (include/aeron_cluster/sbe_messages.hpp:332-406) of every record of
+ * a parse-mode decode, and classify_topic (include/aeron_cluster/topic_router.hpp) of its topic.
+ * pred[i] is a set of: */
+#define SBE_PR_SESSION_EVENT 0x1u  /* is_session_event(): template 2, schema 111 */
+#define SBE_PR_TOPIC_MESSAGE 0x2u  /* is_topic_message(): template 1 and schema 1 or 111; template 2 and schema 1;
+                                      or a message type that contains "ORDER" or "TopicMessage" */
+#define SBE_PR_ACKNOWLEDGMENT 0x4u /* is_acknowledgment(): template 2, schema 1 */
+#define SBE_PR_ORDER_MESSAGE 0x8u  /* is_order_message(): is_topic_message() and a type that contains "ORDER", or
+                                      a payload that contains order_details, token_pair, quantity, side or
+                                      client_order_id */
+/* topic_class[i]: classify_topic of view 0 of an SBE_ST_TM record (0 for any other record) */
+#define SBE_TC_UNKNOWN 0u
+#define SBE_TC_ORDERS 1u  /* "orders", "order_request_topic" */
+#define SBE_TC_CONTROL 2u /* "_subscriptions", "_ack", "_control", "_internal" */
+
+typedef struct sbe_select_out { /* device arrays */
+    uint8_t* pred;        /* [n] SBE_PR_* */
+    uint8_t* select;      /* [n] or NULL: 1 for an SBE_ST_TM record with SBE_PR_ORDER_MESSAGE (the callback's test
+                             for the records sbe_json_extract_batch and sbe_delivery_keys serve; its CREATE_ORDER
+                             clause is implied by the "ORDER" search), else 0 */
+    uint8_t* topic_class; /* [n] or NULL: SBE_TC_* */
+    uint64_t* totals;     /* [2] {records with select 1, records with SBE_PR_ORDER_MESSAGE}, zeroed by the call
+                             (8-B aligned) */
+} sbe_select_out;
+
+/* The predicates are those of the ParseResult the record decodes to: an SBE_ST_TM has message type
+ * view 1 and payload view 3; an SBE_ST_ACK the type "Acknowledgment" and payload view 1 ("SUCCESS"
+ * under SBE_FL_PAYLOAD_DEFAULT), and being template 2 / schema 1 it is a topic message to the
+ * reference, so an Ack whose payload contains "side" has SBE_PR_ORDER_MESSAGE (select stays 0); an
+ * SBE_ST_SESSION_EVENT the type "SessionEvent" and payload view 3; an error status has no strings and
+ * an all-zero header (SBE_ST_ERR_UNKNOWN_TYPE keeps hdr); a status the parse mode does not produce
+ * gives pred 0.  Matching is on bytes, case-sensitive, and a match lies wholly inside its view; views
+ * are kept inside their records whatever the descriptors say.  in / rec_off / dec: the arguments and
+ * outputs of the decode call; dec->status, flags, hdr, view_off and view_len are read (ts and seq may
+ * be null).  One launch after a memset of totals, no workspace; every element i < n of each non-null
+ * array is written and nothing else.  n == 0 is SBE_OK with totals zeroed: only out and out->totals
+ * are looked at.  SBE_EINVAL (before any launch, nothing written): a null pointer (select and
+ * topic_class excepted), n >= 2^32, rec_off or totals not 8-byte, hdr not 2-byte or a view array not
+ * 4-byte aligned. */
+int sbe_order_select(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
+                     const sbe_select_out* out, void* stream);
+/* Bytes of the kernel's LDS window (a multiple of 16): a payload that crosses it is searched in
+ * overlapping rounds.  For callers and tests that want records on either side of that edge. */
+uint32_t sbe_order_select_window(void);
 
 /* ================================ delivery reports ================================ */
 /* The read side of the tables above: what examples/pubsub_reconnect_test.cpp prints from its sets

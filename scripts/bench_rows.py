@@ -22,6 +22,10 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
   json_extract           1 M decoded fixed-256 Orders, the nine order-id member paths read out of every
                          payload (sbe_json_extract_batch), flat and nested payloads, and in the same run
                          sbe_classify_commits on the same buffers (same staging, no record parsed)
+  order_select           1 M decoded fixed-256 Orders, the ParseResult predicates, the subscriber's order test
+                         and the topic class per record (sbe_order_select): CREATE_ORDER types (no payload
+                         searched) and an empty type with nested payloads (every payload searched), and the
+                         host loop over ParseResults it replaces, timed on the CPU in the same row
   ack_correlate          1 M "pub_<nanos>" uuids remembered in a 2 M-slot in-flight table, then 1 M full
                          acks (about 10 % unknown ids, 1 % repeated ids) decoded on-egress and matched;
                          remember, match and the decode of the same ack batch timed in the same run, and
@@ -572,6 +576,64 @@ def row_json_extract(steps, warmup):
         torch.cuda.empty_cache()
 
 
+def row_order_select(steps, warmup):
+    """sbe_order_select after a parse_message decode of 1 M fixed-256 Orders: with CREATE_ORDER types
+    (every record is decided by its type: no payload is staged or searched) and with an empty type
+    and the nested payload of the json_extract row (every payload is searched; the needle lies 75
+    bytes in).  Bytes: 46 B of descriptors (rec_off 8, status 1, flags 1, hdr 4, the offsets and
+    lengths of views 0, 1 and 3 24) and 3 B of outputs a record, the type and topic read, and in
+    the full-search case the payloads.  CPU, in the same row: the
+    host loop the call replaces (ParsedBatch::result_into + the predicates per record,
+    tests/select/select_baseline), one thread and CPU_THREADS threads."""
+    import subprocess
+    n = 1_000_000
+    arena, L, ts = T.fixed256_orders(n)
+    nested = (b'{"uuid":"cid_0123456789abcdefg","message":{"message":{"order_details":'
+              b'{"client_order_id":"cid_0123456789abcdefg"}}}}')
+    full = arena.reshape(n, 222).copy()
+    full[:, 47:190] = np.frombuffer(nested.ljust(143), np.uint8)
+    # an empty type: its 12 bytes go to the uuid, the record keeps its 256 bytes
+    L_full = np.asarray(L, np.uint32).reshape(n, 5).copy()
+    L_full[:, 1], L_full[:, 2] = 0, 41
+    for which, (name, ar, ln) in enumerate((("skipped_search", arena, L), ("full_search", full.reshape(-1), L_full))):
+        data, off = T.oracle_encode(ar, ln, ts)[:2]
+        d0, o0 = dev(data, torch.uint8), dev(np.asarray(off, np.uint64), torch.int64)
+
+        def make(k):
+            d, o = d0.clone(), o0.clone()
+            dec = sbecodec.decode_batch(d, o, sbecodec.DEC_PARSE_MESSAGE, out=sbecodec.alloc_decoded(n, "cuda"),
+                                        in_bytes=data.size)
+            return d, o, dec, sbecodec.order_select(d, o, dec)
+        R = Rot(make)
+        torch.cuda.synchronize()
+        dec0, got0 = R.sets[0][2], R.sets[0][3].numpy()
+        pbytes = int(dec0.view_len[:n, 3].to(torch.int64).sum().item()) if which else 0
+        tbytes = int(dec0.view_len[:n, :2].to(torch.int64).sum().item())
+        assert got0["totals"].tolist() == [n, n], got0["totals"]
+
+        def fn():
+            d, o, dec, out = R.next()
+            sbecodec.order_select(d, o, dec, out=out)
+        ms = _event_ms(fn, steps, warmup)
+        extra = {"row": f"order_select_{name}", "payload_bytes": pbytes, "payload_GBps": pbytes / (ms * 1e-3) / 1e9,
+                 "pred_counts": np.bincount(got0["pred"], minlength=16).tolist(),
+                 "class_counts": np.bincount(got0["topic_class"], minlength=3).tolist()}
+        if not NO_CPU:
+            dd = os.path.join(ROOT, "tests", "select")
+            subprocess.run(["make", "-s", "-C", dd, "select_baseline"], check=True)
+            for th in (1, CPU_THREADS):
+                cpu = json.loads(subprocess.run([os.path.join(dd, "select_baseline"), str(n), str(which), str(th)], check=True,
+                                                capture_output=True, text=True).stdout)
+                assert cpu["selected"] == n and cpu["record_bytes"] == 256, cpu
+                extra[f"cpu_mask_loop_ms_{th}_threads"] = cpu["mask_loop_ms"]
+            extra["cpu_over_device"] = extra[f"cpu_mask_loop_ms_{CPU_THREADS}_threads"] / ms
+        print(json.dumps(extra), flush=True)
+        line(f"order_select_{name}", n, ms * 1e-3,
+             {"sbe_order_select (memset + 1 launch)": (ms, pbytes + tbytes + (46 + 3) * n)})
+        del R
+        torch.cuda.empty_cache()
+
+
 def row_commit_emit(steps, warmup):
     """sbe_emit_commit_offsets over 1 M decoded and classified fixed-256 Orders whose headers all
     carry a known topic (every record emits a session-framed CommitOffsetLite; short identifiers),
@@ -1001,7 +1063,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,commit_emit,commit_fallback,ack_correlate,delivery_track,delivery_report")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,order_select,commit_emit,commit_fallback,ack_correlate,delivery_track,delivery_report")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -1032,6 +1094,8 @@ def main():
             row_autocommit(args.steps, args.warmup)
         elif r == "json_extract":
             row_json_extract(args.steps, args.warmup)
+        elif r == "order_select":
+            row_order_select(args.steps, args.warmup)
         elif r == "commit_emit":
             row_commit_emit(args.steps, args.warmup)
         elif r == "commit_fallback":
