@@ -4374,6 +4374,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 #include "delivery_keys.hpp"
 #include "delivery_report.hpp"
 #include "order_select.hpp"
+#include "term_scan.hpp"
 
 }  // namespace
 
@@ -5451,6 +5452,45 @@ int sbe_reassemble_fragments(const uint8_t* in, const uint64_t* frag_off, const 
 #define SBE_FC_MAXB 4096
 #endif
     hipLaunchKernelGGL(frag_copy, dim3((uint32_t)(cb < SBE_FC_MAXB ? cb : SBE_FC_MAXB)), dim3(256), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+uint32_t sbe_term_scan_tile(void) { return kTsTileBytes; }
+
+size_t sbe_term_scan_workspace_size(uint64_t block_bytes) {
+    // exit / fragments / bytes per entry slot, the visited tiles, their count; each piece on 16 bytes
+    const uint64_t tiles = (block_bytes + kTsTileBytes - 1) / kTsTileBytes;
+    return (size_t)(tiles * kTsSlots * 12 + tiles * sizeof(uint4) + 16 + 5 * 16);
+}
+
+int sbe_term_scan(const uint8_t* block, uint64_t block_bytes, uint64_t start, uint64_t fragment_limit,
+                  uint64_t frag_capacity, uint8_t* out, const sbe_term_out* o, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!o || !o->counts || !o->frag_off || !o->flags) return SBE_EINVAL;
+    if ((block_bytes & 31) || (start & 31) || start > block_bytes || block_bytes > kTsMaxBlock) return SBE_EINVAL;
+    if (misaligned(block, 15) || misaligned(o->frag_off, 7) || misaligned(o->counts, 7) || misaligned(o->frag_src, 3))
+        return SBE_EINVAL;
+    if (block_bytes > start && (!block || !workspace)) return SBE_EINVAL;
+    if (block_bytes > start && workspace_bytes < sbe_term_scan_workspace_size(block_bytes)) return SBE_ENOSPC;
+    const uint64_t limit = fragment_limit < frag_capacity ? fragment_limit : frag_capacity;
+    if (limit == 0 || block_bytes == start) {
+        hipLaunchKernelGGL(term_counts_only, dim3(1), dim3(1), 0, s, o->counts, o->frag_off, start,
+                           limit == 0 ? SBE_TERM_STOP_LIMIT : SBE_TERM_STOP_END);
+        return record_hip(hipGetLastError());
+    }
+    const uint64_t tiles = (block_bytes + kTsTileBytes - 1) / kTsTileBytes;
+    const uint32_t tile0 = (uint32_t)(start / kTsTileBytes), nt = (uint32_t)tiles - tile0;
+    Carver ws(workspace);
+    TsArgs a{block, block_bytes, start, limit, out, o->frag_off, o->flags, o->frag_src, o->counts};
+    a.w_exit = ws.take<uint32_t>(tiles * kTsSlots);
+    a.w_frags = ws.take<uint32_t>(tiles * kTsSlots);
+    a.w_bytes = ws.take<uint32_t>(tiles * kTsSlots);
+    a.visited = ws.take<uint4>(tiles);
+    a.nvisited = ws.take<uint32_t>(1);
+    hipLaunchKernelGGL(term_tile_chain, dim3(nt), dim3(kTsSlots), 0, s, a, tile0);
+    hipLaunchKernelGGL(term_walk_tiles, dim3(1), dim3(kWave), 0, s, a);
+    hipLaunchKernelGGL(term_emit, dim3(nt), dim3(kTsSlots), 0, s, a);
     return record_hip(hipGetLastError());
 }
 

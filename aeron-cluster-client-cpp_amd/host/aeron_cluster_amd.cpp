@@ -3030,6 +3030,76 @@ EncodedBatch FragmentReassembler::on_fragments(const std::uint8_t* data, const s
     return b;
 }
 
+EncodedBatch FragmentReassembler::on_term_block(const std::uint8_t* block, std::size_t len, std::size_t start,
+                                                std::size_t limit, std::size_t* next) {
+    if ((len & 31) || (start & 31) || start > len) throw std::invalid_argument("on_term_block: block and start are multiples of 32");
+    Ctx& c = ctx();
+    Pipeline::Slot& s = c.pipe.slot[0];  // as on_fragments
+    hipStream_t stream = c.batch_stream();
+    // the accumulator so far goes first as a frame of its own: a middle fragment (flags 0, a data
+    // frame), which the walk delivers ahead of the block's and reassembly appends to or clears
+    // exactly as on_fragments' leading fragment
+    const size_t body = len - start, pre = acc_.empty() ? 0 : ((32 + acc_.size() + 31) & ~(size_t)31);
+    const size_t total = pre + body;
+    if (total > ((size_t)1 << 30)) throw std::invalid_argument("on_term_block: more than 2^30 bytes");
+    const uint64_t lim = pre && limit != ~(size_t)0 ? (uint64_t)limit + 1 : (uint64_t)limit;
+    const uint64_t cap = lim < total / 32 ? lim : total / 32;
+    s.d_in.need(total + 16);
+    if (pre) {
+        s.pin.need(pre);
+        uint8_t* hp = s.pin.b();
+        std::memset(hp, 0, pre);
+        const int32_t L = (int32_t)(32 + acc_.size());
+        const uint16_t type = 1;
+        std::memcpy(hp, &L, 4);
+        std::memcpy(hp + 6, &type, 2);
+        std::memcpy(hp + 32, acc_.data(), acc_.size());
+        hip_check(hipMemcpyAsync(s.d_in.p, hp, pre, hipMemcpyHostToDevice, stream), "H2D");
+    }
+    if (body) hip_check(hipMemcpyAsync(s.d_in.b() + pre, block + start, body, hipMemcpyHostToDevice, stream), "H2D");
+    const size_t o_off = al16(total), o_fl = o_off + (cap + 1) * 8, o_cnt = al16(o_fl + cap), o_ws = o_cnt + 32;
+    const size_t wsb = sbe_term_scan_workspace_size(total);
+    s.d_out.need(o_ws + wsb + 16);
+    uint8_t* dfr = s.d_out.b();
+    const sbe_term_out to{reinterpret_cast<uint64_t*>(dfr + o_off), dfr + o_fl, nullptr, reinterpret_cast<uint64_t*>(dfr + o_cnt)};
+    if (sbe_term_scan(s.d_in.b(), total, 0, lim, cap, dfr, &to, dfr + o_ws, wsb, stream) != SBE_OK) fail("sbe_term_scan");
+    c.h_aux.need(48);
+    uint64_t* counts = reinterpret_cast<uint64_t*>(c.h_aux.p);
+    hip_check(hipMemcpyAsync(counts, to.counts, 32, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    const uint64_t nf = counts[0], payload = counts[2];
+    if (next) *next = start + (size_t)counts[1] - pre;  // the accumulator's frame is always consumed (lim >= 1 with it)
+    EncodedBatch b;
+    if (nf == 0) {
+        b.offsets = HostBytesAccess::make<uint64_t>(1);
+        b.offsets[0] = 0;
+        return b;
+    }
+    const size_t d_off = al16(payload), d_cnt = d_off + (nf + 1) * 8, d_ws = al16(d_cnt + 16);
+    const size_t rwb = sbe_reassemble_workspace_size(nf);
+    c.d_aux.need(d_ws + rwb + 16);
+    uint8_t* dout = static_cast<uint8_t*>(c.d_aux.p);
+    uint64_t* dmo = reinterpret_cast<uint64_t*>(dout + d_off);
+    uint64_t* dcnt = reinterpret_cast<uint64_t*>(dout + d_cnt);
+    if (sbe_reassemble_fragments(dfr, to.frag_off, to.flags, nf, dout, dmo, dcnt, dout + d_ws, rwb, stream) != SBE_OK)
+        fail("sbe_reassemble_fragments");
+    hip_check(hipMemcpyAsync(counts + 4, dcnt, 16, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    const uint64_t m = counts[4], carry = counts[5];
+    b.offsets = HostBytesAccess::make<uint64_t>(m + 1);
+    b.status = HostBytesAccess::make<uint8_t>(m);
+    HostBytesAccess::zero(b.status);
+    hip_check(hipMemcpyAsync(b.offsets.data(), dmo, (m + 1) * 8, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    const uint64_t msg_bytes = b.offsets[m];
+    b.bytes = HostBytesAccess::make((size_t)msg_bytes);
+    acc_.resize(carry);
+    if (msg_bytes) hip_check(hipMemcpyAsync(b.bytes.data(), dout, msg_bytes, hipMemcpyDeviceToHost, stream), "D2H");
+    if (carry) hip_check(hipMemcpyAsync(acc_.data(), dout + msg_bytes, carry, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    return b;
+}
+
 MessageHandler::MessageHandler() = default;
 MessageHandler::~MessageHandler() = default;
 

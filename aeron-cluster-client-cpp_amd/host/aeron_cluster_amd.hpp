@@ -865,10 +865,30 @@ std::optional<LiteRecord> decode_lite(const std::uint8_t* data, std::size_t len)
 // i is data[frag_off[i], frag_off[i+1]) with header flags[i] (BEGIN 0x80, END 0x40).  Returns the
 // delivered messages in order; a message whose END has not arrived yet is kept for the next call,
 // exactly as the reference's accumulator.
+//
+// A raw block of a term buffer (whole frames with their 32-byte Aeron data-frame headers, as an
+// image's block or raw poll hands them, or a host_register'ed term buffer read in place) is framed
+// first: term_walk is the poll's loop over the headers on one host thread (the frame layer is
+// third-party Aeron, restated from the data-frame layout, see sbe_term_scan in sbecodec.h), and
+// on_term_block runs the same walk (sbe_term_scan) and the reassembly on the device.  block, len
+// and start are multiples of 32 (std::invalid_argument otherwise).
+struct TermFragments {
+    std::vector<std::uint64_t> frag_off;  // [fragments + 1] offsets of the payloads laid back to back
+    std::vector<std::uint8_t> flags;      // header byte 5 of each delivered frame
+    std::vector<std::uint32_t> frag_src;  // offset of each delivered frame's header in the block
+    std::uint64_t next = 0;               // the offset the walk stopped at
+    std::uint32_t stop = 0;               // SBE_TERM_STOP_*
+};
+TermFragments term_walk(const std::uint8_t* block, std::size_t len, std::size_t start, std::size_t limit);
+
 class FragmentReassembler {
 public:
     EncodedBatch on_fragments(const std::uint8_t* data, const std::uint64_t* frag_off, const std::uint8_t* flags,
                               std::size_t n);
+    // The fragments of block[start, len), at most `limit` of them, reassembled; *next: where the
+    // walk stopped (the start of the next call).  The carry is kept exactly as on_fragments keeps it.
+    EncodedBatch on_term_block(const std::uint8_t* block, std::size_t len, std::size_t start, std::size_t limit,
+                               std::size_t* next = nullptr);
     std::size_t pending_bytes() const { return acc_.size(); }
 
 private:

@@ -146,6 +146,10 @@ class _SelectOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("pred", "select", "topic_class", "totals")]
 
 
+class _TermOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("frag_off", "flags", "frag_src", "counts")]
+
+
 class _KeyListOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("count", "key", "len", "value", "answered")]
 
@@ -278,6 +282,14 @@ def _load():
                                      ctypes.POINTER(_SelectOut), ctypes.c_void_p]
     lib.sbe_order_select_window.restype = ctypes.c_uint32
     lib.sbe_order_select_window.argtypes = []
+    lib.sbe_term_scan_workspace_size.restype = ctypes.c_size_t
+    lib.sbe_term_scan_workspace_size.argtypes = [ctypes.c_uint64]
+    lib.sbe_term_scan_tile.restype = ctypes.c_uint32
+    lib.sbe_term_scan_tile.argtypes = []
+    lib.sbe_term_scan.restype = ctypes.c_int
+    lib.sbe_term_scan.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                  ctypes.c_void_p, ctypes.POINTER(_TermOut), ctypes.c_void_p, ctypes.c_size_t,
+                                  ctypes.c_void_p]
     lib.sbe_inflight_list_workspace_size.restype = ctypes.c_size_t
     lib.sbe_inflight_list_workspace_size.argtypes = [ctypes.c_uint32]
     lib.sbe_inflight_list_keys.restype = ctypes.c_int
@@ -1512,6 +1524,67 @@ def reassemble(data, frag_off, flags, out=None, msg_off=None, workspace=None, st
                                         _ptr(counts), _ptr(workspace), workspace.numel(), _stream(stream))
     _check(rc, "sbe_reassemble_fragments")
     return Reassembled(out, msg_off, counts)
+
+
+# sbe_term_scan: why the walk stopped (counts[3])
+TERM_STOP_END, TERM_STOP_LIMIT, TERM_STOP_UNCOMMITTED, TERM_STOP_SHORT, TERM_STOP_PARTIAL = range(5)
+TERM_MAX_BLOCK = 1 << 30
+
+
+@dataclass
+class TermFragments:
+    out: torch.Tensor | None       # uint8: the payloads back to back in delivery order
+    frag_off: torch.Tensor         # int64 [capacity + 1]: fragment i = out[frag_off[i]:frag_off[i+1]]
+    flags: torch.Tensor            # uint8 [capacity]: header byte 5 (BEGIN 0x80, END 0x40)
+    frag_src: torch.Tensor | None  # int32 [capacity] (u32): offset of each delivered frame's header in block
+    counts: torch.Tensor           # int64 [4]: fragments, next, payload bytes, TERM_STOP_*
+
+
+def term_scan_tile() -> int:
+    """Bytes of block one workgroup of sbe_term_scan chains in LDS."""
+    return int(lib().sbe_term_scan_tile())
+
+
+def term_scan(block, start=0, limit=None, stream=None, capacity=None, out=None, want_out=True, want_src=True,
+              workspace=None) -> TermFragments:
+    """The fragments a poll of one image finds in a raw term-buffer block (whole frames with their
+    32-byte Aeron data-frame headers), from offset `start`, at most `limit`: out / frag_off / flags
+    and counts[0] are what reassemble takes.  block.numel() and start are multiples of 32.  capacity:
+    entries of the tables (default: every slot of the block could be a fragment, or `limit`); out: a
+    tensor of block.numel() - start bytes to write the payloads to (want_out=False: tables only)."""
+    block = _dev(block, torch.uint8, "block")
+    nb = int(block.numel())
+    dev = block.device
+    start = int(start)
+    if start < 0 or start > nb or (limit is not None and int(limit) < 0) or (capacity is not None and int(capacity) < 0):
+        raise SbeError("term_scan: start must lie in [0, block.numel()], limit and capacity must not be negative")
+    if capacity is None:
+        # one more than the block has slots: the effective limit is min(limit, capacity), and a walk
+        # without a limit must not stop at one
+        capacity = (nb - start) // 32 + 1
+        if limit is not None:
+            capacity = min(capacity, int(limit))
+    lim = (1 << 64) - 1 if limit is None else int(limit)
+    if not want_out:
+        out = None
+    elif out is None:
+        out = torch.empty(max(nb - start, 16), dtype=torch.uint8, device=dev)
+    elif _dev(out, torch.uint8, "out").numel() < nb - start:
+        raise SbeError("term_scan: out holds fewer than block.numel() - start bytes")
+    frag_off = torch.empty(capacity + 1, dtype=torch.int64, device=dev)
+    flags = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
+    frag_src = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev) if want_src else None
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    need = int(lib().sbe_term_scan_workspace_size(nb))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    o = _TermOut(frag_off.data_ptr(), flags.data_ptr(), None if frag_src is None else frag_src.data_ptr(),
+                 counts.data_ptr())
+    rc = lib().sbe_term_scan(_ptr(block) if nb else None, nb, int(start), lim, capacity,
+                             None if out is None else _ptr(out), ctypes.byref(o), _ptr(workspace), workspace.numel(),
+                             _stream(stream))
+    _check(rc, "sbe_term_scan")
+    return TermFragments(out, frag_off, flags[:capacity], None if frag_src is None else frag_src[:capacity], counts)
 
 
 # bytes per order of the default output bound (a record is at most ~800 B plus its escaped strings:

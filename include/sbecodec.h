@@ -86,6 +86,9 @@
  *                                  is_topic_message / is_session_event / is_acknowledgment
  *                                  include/aeron_cluster/sbe_messages.hpp:332-406 per record, and
  *                                  classify_topic include/aeron_cluster/topic_router.hpp
+ * sbe_term_scan()                 no reference source (third-party Aeron, TermReader::read): the walk
+ *                                  over the 32-byte data-frame headers of a term-buffer block that
+ *                                  hands fragments to onFragment src/cluster_client.cpp:39-82
  * sbe_inflight_list_keys()        printMessageComparison examples/pubsub_reconnect_test.cpp:130-204 and
  *                                  printClientOrderAudit :206-274: the ids sent and never received, or
  *                                  received and never sent, the first ones in std::set order; with a
@@ -1006,6 +1009,55 @@ size_t sbe_reassemble_workspace_size(uint64_t n);
 int sbe_reassemble_fragments(const uint8_t* in, const uint64_t* frag_off, const uint8_t* flags, uint64_t n,
                              uint8_t* out, uint64_t* msg_off, uint64_t* counts, void* workspace,
                              size_t workspace_bytes, void* stream);
+
+/* ============================ Aeron term-buffer framing ============================ */
+/* The step in front of sbe_reassemble_fragments: the walk a poll of one image does over a raw block
+ * of a term buffer (Aeron's TermReader::read loop), which finds the fragments.  The frame layer is
+ * third-party Aeron, which the reference tree does not carry: the semantics are restated here from
+ * the data-frame layout, not pinned to a reference source.  A frame starts on a 32-byte boundary
+ * with a 32-byte little-endian header:
+ *   [0] i32 frame_length (header + payload, without alignment padding; <= 0: not yet committed)
+ *   [4] i8 version  [5] u8 flags (SBE_FRAG_BEGIN / SBE_FRAG_END)  [6] u16 type (0: padding frame)
+ *   [8] i32 term_offset  [12] i32 session_id  [16] i32 stream_id  [20] i32 term_id  [24] i64 reserved
+ * and the next frame starts align(frame_length, 32) bytes on.  The walk:
+ *   offset = start; fragments = 0
+ *   while fragments < limit and offset < block_bytes:
+ *       L = frame_length at offset
+ *       L <= 0: stop UNCOMMITTED.  L < 32: stop SHORT.  offset + align(L, 32) > block_bytes: stop PARTIAL
+ *       (the last two are this library's: it never reads outside the block whatever the bytes say)
+ *       offset += align(L, 32); a frame whose type is not 0 is delivered: payload = the L - 32 bytes
+ *       after its header, flags = its byte 5, fragments += 1 (a padding frame is consumed uncounted)
+ *   stop LIMIT when fragments == limit, else END
+ * with limit = min(fragment_limit, frag_capacity).  A frame that stops the walk is not consumed.
+ * Payload bytes that look like headers are never frames: only the chain from `start` counts.
+ * Outputs (device memory): the payloads back to back in delivery order in out (block_bytes - start
+ * bytes are always enough; NULL: tables only), fragment i at out[frag_off[i] .. frag_off[i+1]),
+ * frag_off[0] = 0, flags[i], frag_src[i] = the offset of its frame header in block (or NULL);
+ * counts = {fragments, next (the offset the walk stopped at), payload bytes, SBE_TERM_STOP_*}.
+ * out / frag_off / flags / counts[0] are the in / frag_off / flags / n of sbe_reassemble_fragments.
+ * SBE_EINVAL (before anything touches a device): null o / counts / frag_off / flags; block_bytes or
+ * start not a multiple of 32; start > block_bytes; block_bytes > 2^30; block not 16-B, frag_off /
+ * counts not 8-B, frag_src not 4-B aligned; null block or workspace when block_bytes > start.
+ * SBE_ENOSPC: block_bytes > start and workspace_bytes < sbe_term_scan_workspace_size(block_bytes).
+ * block_bytes == start or limit == 0: one launch that writes counts and frag_off[0]; otherwise
+ * three launches on `stream`. */
+#define SBE_TERM_STOP_END 0u
+#define SBE_TERM_STOP_LIMIT 1u
+#define SBE_TERM_STOP_UNCOMMITTED 2u
+#define SBE_TERM_STOP_SHORT 3u
+#define SBE_TERM_STOP_PARTIAL 4u
+typedef struct sbe_term_out {
+    uint64_t* frag_off; /* [frag_capacity + 1] offsets of the compacted payloads in `out` */
+    uint8_t* flags;     /* [frag_capacity] header byte 5 of each delivered frame */
+    uint32_t* frag_src; /* [frag_capacity] or NULL: offset of each delivered frame's header in block */
+    uint64_t* counts;   /* [4] fragments, next, payload bytes, stop reason */
+} sbe_term_out;
+size_t sbe_term_scan_workspace_size(uint64_t block_bytes);
+/* bytes of block one workgroup chains in LDS (a multiple of 32) */
+uint32_t sbe_term_scan_tile(void);
+int sbe_term_scan(const uint8_t* block, uint64_t block_bytes, uint64_t start, uint64_t fragment_limit,
+                  uint64_t frag_capacity, uint8_t* out, const sbe_term_out* o, void* workspace,
+                  size_t workspace_bytes, void* stream);
 
 /* ========================== Order JSON (publish_order payload) ========================== */
 /* Replaces Order::to_json (src/order_types.cpp:122-181, jsoncpp StreamWriterBuilder with

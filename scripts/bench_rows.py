@@ -26,6 +26,10 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
                          and the topic class per record (sbe_order_select): CREATE_ORDER types (no payload
                          searched) and an empty type with nested payloads (every payload searched), and the
                          host loop over ParseResults it replaces, timed on the CPU in the same row
+  term_scan              a raw 16 MiB term-buffer block (config-3 records, session-framed, long messages in
+                         frames of at most 1376 bytes) framed on the device (sbe_term_scan): the scan alone,
+                         tables only, scan + reassembly, a device copy of the payload as the ceiling, and the
+                         host mirror's one-thread term_walk with its payload memcpy
   ack_correlate          1 M "pub_<nanos>" uuids remembered in a 2 M-slot in-flight table, then 1 M full
                          acks (about 10 % unknown ids, 1 % repeated ids) decoded on-egress and matched;
                          remember, match and the decode of the same ack batch timed in the same run, and
@@ -634,6 +638,87 @@ def row_order_select(steps, warmup):
         torch.cuda.empty_cache()
 
 
+def row_term_scan(steps, warmup):
+    """sbe_term_scan over a raw 16 MiB term-buffer block: config-3 records, session-framed, one
+    BEGIN|END frame each, with every 64th message a 6 KB TopicMessage in BEGIN / middle / END frames of
+    at most 1376 payload bytes.  Timed in the same run: the scan alone (tables and payload copy), the
+    scan with tables only, scan + sbe_reassemble_fragments, a device copy of the payload bytes (the
+    ceiling), and on the host the mirror's one-thread term_walk alone and with its payload memcpy
+    (tests/term/term_baseline)."""
+    import subprocess
+    import tempfile
+    import termscan_lib as S
+    total = 16 << 20
+    data, off = T.mixed_records(60_000)
+    b = S.Block()
+    long_payload = bytes(32 + j % 90 for j in range(6000))
+    nmsg = 0
+    for i in range(60_000):
+        rec = bytes(data[int(off[i]):int(off[i + 1])])
+        if i % 64 == 63:
+            rec = T.tm_wire((b"orders", b"CREATE_ORDER", b"msg_%025d" % i, long_payload, b"{}"), 1_760_000_000_000 + i)
+        rec = T.session_wrap(rec)
+        if len(b) + 32 * ((len(rec) + 1375) // 1376) + S.align(len(rec)) + 64 > total:
+            break
+        for k in range(0, len(rec), 1376):
+            b.frame(rec[k: k + 1376], (S.BEGIN if k == 0 else 0) | (S.ENDF if k + 1376 >= len(rec) else 0))
+        nmsg += 1
+    b.pad_to(total)
+    blk = b.bytes()
+    w = S.walk(blk)
+    n, pbytes = w["fragments"], w["frag_off"][-1]
+    d0 = torch.from_numpy(np.frombuffer(blk, np.uint8).copy()).cuda()
+    ws = torch.empty(int(sbecodec.lib().sbe_term_scan_workspace_size(total)), dtype=torch.uint8, device="cuda")
+    rws = torch.empty(int(sbecodec.lib().sbe_reassemble_workspace_size(n)), dtype=torch.uint8, device="cuda")
+    R = Rot(lambda k: (d0.clone(), torch.empty(total, dtype=torch.uint8, device="cuda"),
+                       torch.empty(total, dtype=torch.uint8, device="cuda"), torch.empty(n + 1, dtype=torch.int64, device="cuda")))
+    first = sbecodec.term_scan(d0, workspace=ws)
+    torch.cuda.synchronize()
+    c = first.counts.cpu().numpy()
+    assert (int(c[0]), int(c[1]), int(c[2]), int(c[3])) == (n, total, pbytes, S.END), c
+    assert first.out[:pbytes].cpu().numpy().tobytes() == w["payload"]
+
+    def scan():
+        d, out, _, _ = R.next()
+        return sbecodec.term_scan(d, out=out, capacity=n + 1, workspace=ws)
+
+    def tables():
+        d, _, _, _ = R.next()
+        sbecodec.term_scan(d, capacity=n + 1, want_out=False, workspace=ws)
+
+    def chain():  # n: the fragment count a caller reads from counts[0] (here known from the first call)
+        d, out, out2, mo = R.next()
+        s = sbecodec.term_scan(d, out=out, capacity=n + 1, workspace=ws)
+        sbecodec.reassemble(s.out, s.frag_off[: n + 1], s.flags[:n], out=out2, msg_off=mo, workspace=rws)
+
+    def copy():
+        d, out, _, _ = R.next()
+        out[:pbytes].copy_(d[:pbytes])
+
+    ms_scan, ms_tab, ms_chain, ms_copy = (_event_ms(f, steps, warmup) for f in (scan, tables, chain, copy))
+    extra = {"row": "term_scan_detail", "block_bytes": total, "fragments": n, "messages": nmsg, "payload_bytes": pbytes,
+             "scan_ms": ms_scan, "scan_tables_only_ms": ms_tab, "scan_reassemble_ms": ms_chain, "device_copy_ms": ms_copy,
+             "launches": "term_tile_chain, term_walk_tiles, term_emit", "tile_bytes": sbecodec.term_scan_tile(),
+             "tiles": total // sbecodec.term_scan_tile()}
+    if not NO_CPU:
+        dd = os.path.join(ROOT, "tests", "term")
+        subprocess.run(["make", "-s", "-C", dd, "term_baseline"], check=True)
+        with tempfile.NamedTemporaryFile(suffix=".bin") as tf:
+            tf.write(blk)
+            tf.flush()
+            cpu = json.loads(subprocess.run([os.path.join(dd, "term_baseline"), tf.name], check=True, capture_output=True,
+                                            text=True).stdout)
+        assert cpu["fragments"] == n and cpu["payload_bytes"] == pbytes
+        extra["host_term_walk_ms"] = cpu["term_walk_ms"]
+        extra["host_term_walk_memcpy_ms"] = cpu["term_walk_memcpy_ms"]
+        set_cpu(n / (cpu["term_walk_memcpy_ms"] * 1e-3), "the same block, host mirror term_walk + payload memcpy, 1 thread "
+                "(sequential by definition)", cores=1)
+    print(json.dumps(extra), flush=True)
+    # the block's header sectors read twice (chain, emit), payload read and written, 12 B per slot
+    # written and 12 B per tile entry read, the tables written
+    line("term_scan", n, ms_scan * 1e-3, {"sbe_term_scan (3 launches)": (ms_scan, 2 * total + 2 * pbytes + 12 * (total // 32) + 13 * n)})
+
+
 def row_commit_emit(steps, warmup):
     """sbe_emit_commit_offsets over 1 M decoded and classified fixed-256 Orders whose headers all
     carry a known topic (every record emits a session-framed CommitOffsetLite; short identifiers),
@@ -1063,7 +1148,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,order_select,commit_emit,commit_fallback,ack_correlate,delivery_track,delivery_report")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,order_select,term_scan,commit_emit,commit_fallback,ack_correlate,delivery_track,delivery_report")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -1096,6 +1181,8 @@ def main():
             row_json_extract(args.steps, args.warmup)
         elif r == "order_select":
             row_order_select(args.steps, args.warmup)
+        elif r == "term_scan":
+            row_term_scan(args.steps, args.warmup)
         elif r == "commit_emit":
             row_commit_emit(args.steps, args.warmup)
         elif r == "commit_fallback":
