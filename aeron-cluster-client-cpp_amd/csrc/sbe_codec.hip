@@ -4375,6 +4375,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 #include "delivery_report.hpp"
 #include "order_select.hpp"
 #include "term_scan.hpp"
+#include "term_append.hpp"
 
 }  // namespace
 
@@ -5491,6 +5492,53 @@ int sbe_term_scan(const uint8_t* block, uint64_t block_bytes, uint64_t start, ui
     hipLaunchKernelGGL(term_tile_chain, dim3(nt), dim3(kTsSlots), 0, s, a, tile0);
     hipLaunchKernelGGL(term_walk_tiles, dim3(1), dim3(kWave), 0, s, a);
     hipLaunchKernelGGL(term_emit, dim3(nt), dim3(kTsSlots), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+uint32_t sbe_term_append_tile(void) { return kTaTile; }
+
+uint64_t sbe_term_frames_length(uint64_t len, uint32_t mtu) {
+    if ((mtu & 31) || mtu < 64 || mtu > 65504) return 0;
+    return ta_required(len, mtu);
+}
+
+size_t sbe_term_append_workspace_size(uint64_t n) {
+    // the tails, two words per plan block, the plan; each piece on 16 bytes
+    const uint64_t nb = (n + 1 + kTaBlk - 1) / kTaBlk;
+    return (size_t)(8 * n + 16 * nb + sizeof(TaPlan) + 4 * 16);
+}
+
+int sbe_term_append(const uint8_t* in, uint64_t in_bytes, const uint64_t* rec_off, uint64_t n, uint8_t* block,
+                    uint64_t block_bytes, uint64_t start, uint64_t limit, uint32_t mtu, uint64_t max_message_length,
+                    const sbe_term_header* hdr, const sbe_term_append_out* o, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!hdr || !o || !o->counts) return SBE_EINVAL;
+    if (n > 0 && (!rec_off || !in || !block || !workspace)) return SBE_EINVAL;
+    if ((block_bytes & 31) || (start & 31) || start > block_bytes || block_bytes > kTaMaxBlock) return SBE_EINVAL;
+    if ((mtu & 31) || mtu < 64 || mtu > 65504 || max_message_length > kTaMaxBlock) return SBE_EINVAL;
+    if (misaligned(block, 15) || misaligned(rec_off, 7) || misaligned(o->rec_tail, 7) || misaligned(o->counts, 7))
+        return SBE_EINVAL;
+    if (n >= (1ull << 32)) return SBE_EINVAL;  // the tails stay below 2^63
+    if (n == 0) {
+        hipLaunchKernelGGL(ta_counts_only, dim3(1), dim3(1), 0, s, o->counts, start);
+        return record_hip(hipGetLastError());
+    }
+    if (workspace_bytes < sbe_term_append_workspace_size(n)) return SBE_ENOSPC;
+    const uint64_t nb = (n + 1 + kTaBlk - 1) / kTaBlk;
+    Carver ws(workspace);
+    TaArgs a{in, in_bytes, rec_off, n, block, block_bytes, start, limit, mtu, max_message_length, *hdr};
+    a.tails = ws.take<uint64_t>(n);
+    if (o->rec_tail) a.tails = o->rec_tail;
+    a.counts = o->counts;
+    a.bsum = ws.take<uint64_t>(nb);
+    a.bmin = ws.take<uint64_t>(nb);
+    a.plan = ws.take<TaPlan>(1);
+    hipLaunchKernelGGL(ta_sums, dim3((uint32_t)nb), dim3(kTaBlk), 0, s, a);
+    hipLaunchKernelGGL(ta_scan_blocks, dim3(1), dim3(kTaBlk), 0, s, a, nb);
+    hipLaunchKernelGGL(ta_tails, dim3((uint32_t)nb), dim3(kTaBlk), 0, s, a);
+    const uint32_t tile0 = (uint32_t)(start / kTaTile), nt = (uint32_t)((block_bytes + kTaTile - 1) / kTaTile) - tile0;
+    if (block_bytes > start) hipLaunchKernelGGL(ta_write, dim3(nt), dim3(kTaThreads), 0, s, a, tile0);
     return record_hip(hipGetLastError());
 }
 

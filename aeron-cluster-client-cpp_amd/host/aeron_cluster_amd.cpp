@@ -3100,6 +3100,59 @@ EncodedBatch FragmentReassembler::on_term_block(const std::uint8_t* block, std::
     return b;
 }
 
+TermAppendResult TermAppender::append_batch(const EncodedBatch& batch, std::size_t first_record, std::uint8_t* block,
+                                            std::size_t len, std::size_t start, const TermAppendOptions& options) {
+    const size_t total = batch.offsets.size() ? batch.offsets.size() - 1 : 0;
+    if (first_record > total) throw std::invalid_argument("append_batch: first_record behind the batch");
+    // the offsets index the batch's bytes as they are
+    return append(batch.bytes.data(), batch.bytes.size(), batch.offsets.data() + first_record, total - first_record, block, len,
+                  start, options);
+}
+
+TermAppendResult TermAppender::append(const std::uint8_t* data, std::size_t nbytes, const std::uint64_t* rec_off, std::size_t n,
+                                      std::uint8_t* block, std::size_t len, std::size_t start, const TermAppendOptions& options) {
+    options.check(len, start);
+    TermAppendResult r;
+    r.next = start;
+    r.stop = SBE_TERM_APPEND_END;
+    if (n == 0) return r;
+    Ctx& c = ctx();
+    Pipeline::Slot& s = c.pipe.slot[0];  // as on_fragments
+    hipStream_t stream = c.batch_stream();
+    // device input: the offsets of the records, then the bytes they index
+    const size_t o_data = al16((n + 1) * 8);
+    s.d_in.need(o_data + nbytes + 16);
+    hip_check(hipMemcpyAsync(s.d_in.p, rec_off, (n + 1) * 8, hipMemcpyHostToDevice, stream), "H2D");
+    if (nbytes) hip_check(hipMemcpyAsync(s.d_in.b() + o_data, data, nbytes, hipMemcpyHostToDevice, stream), "H2D");
+    // device output: the block, the tails, counts, the workspace
+    const size_t o_tail = al16(len), o_cnt = o_tail + n * 8, o_ws = al16(o_cnt + 32);
+    const size_t wsb = sbe_term_append_workspace_size(n);
+    s.d_out.need(o_ws + wsb + 16);
+    uint8_t* d = s.d_out.b();
+    const sbe_term_header h{options.header.session_id, options.header.stream_id, options.header.term_id,
+                            options.header.term_offset_base, options.header.version};
+    const sbe_term_append_out o{reinterpret_cast<uint64_t*>(d + o_tail), reinterpret_cast<uint64_t*>(d + o_cnt)};
+    if (sbe_term_append(s.d_in.b() + o_data, nbytes, reinterpret_cast<const uint64_t*>(s.d_in.p), n, d, len, start, options.limit,
+                        options.mtu, options.effective_max_message_length(len), &h, &o, d + o_ws, wsb, stream) != SBE_OK)
+        fail("sbe_term_append");
+    c.h_aux.need(32);
+    uint64_t* counts = reinterpret_cast<uint64_t*>(c.h_aux.p);
+    hip_check(hipMemcpyAsync(counts, o.counts, 32, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    r.appended = (size_t)counts[0];
+    r.next = counts[1];
+    r.stop = (uint32_t)counts[3];
+    r.rec_tail.resize(r.appended);
+    if (r.appended) hip_check(hipMemcpyAsync(r.rec_tail.data(), o.rec_tail, r.appended * 8, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    // what the call wrote: the frames, and of a padding frame its header
+    const uint64_t data_end = r.appended ? r.rec_tail.back() : start;
+    const uint64_t end = data_end + (r.stop == SBE_TERM_APPEND_TRIPPED && data_end < len ? 32 : 0);
+    if (end > start) hip_check(hipMemcpyAsync(block + start, d + start, end - start, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    return r;
+}
+
 MessageHandler::MessageHandler() = default;
 MessageHandler::~MessageHandler() = default;
 

@@ -895,6 +895,66 @@ private:
     std::vector<std::uint8_t> acc_;
 };
 
+// The publish side of the same frame layer: a batch of encoded records appended to a raw block of a
+// term buffer with Aeron's framing (one BEGIN|END data frame a record, or BEGIN / middle / END frames
+// at the MTU, the padding frame where the term ends), as ExclusivePublication::offer would one
+// record at a time.  Third-party Aeron again, restated and not pinned to a source: the semantics
+// are stated at sbe_term_append in sbecodec.h.  term_append is that loop on one host thread (the
+// role term_walk plays for the scan); TermAppender::append_batch runs sbe_term_append on the device
+// and copies the bytes it wrote, block[start, tail) and a padding header, back into `block`.  Both
+// throw std::invalid_argument where sbe_term_append returns SBE_EINVAL: len or start not a
+// multiple of 32, start > len, len > 2^30, mtu not a multiple of 32 in [64, 65504],
+// max_message_length > 2^30.  This is a batch into a block nobody else writes, not a concurrent
+// publication: there is no ordering between the frames.
+struct TermHeader {
+    std::int32_t session_id = 0;
+    std::int32_t stream_id = 0;
+    std::int32_t term_id = 0;
+    std::int32_t term_offset_base = 0;  // the term offset of block[0] (the block may be a part of a term)
+    std::uint8_t version = 0;
+};
+struct TermAppendOptions {
+    static constexpr std::uint64_t kAeronRule = ~0ull;
+    std::uint32_t mtu = 1408;
+    std::uint64_t limit = ~0ull;                     // a record is refused once the tail is at or behind it
+    std::uint64_t max_message_length = kAeronRule;   // kAeronRule: min(term_length / 8, 16 MiB)
+    std::uint64_t term_length = 0;                   // 0: the block is the whole term
+    TermHeader header;
+    std::uint64_t effective_max_message_length(std::size_t block_len) const {
+        if (max_message_length != kAeronRule) return max_message_length;
+        const std::uint64_t term = term_length ? term_length : block_len, cap = 16ull << 20;
+        return term / 8 < cap ? term / 8 : cap;
+    }
+    // throws std::invalid_argument
+    void check(std::size_t len, std::size_t start) const {
+        if ((len & 31) || (start & 31) || start > len) throw std::invalid_argument("term_append: block and start are multiples of 32");
+        if (len > ((std::size_t)1 << 30)) throw std::invalid_argument("term_append: more than 2^30 bytes");
+        if ((mtu & 31) || mtu < 64 || mtu > 65504) throw std::invalid_argument("term_append: mtu is a multiple of 32 in [64, 65504]");
+        if (effective_max_message_length(len) > (1ull << 30)) throw std::invalid_argument("term_append: max_message_length above 2^30");
+    }
+};
+struct TermAppendResult {
+    std::size_t appended = 0;              // records that went in; the caller goes on with the rest
+    std::uint64_t next = 0;                // the tail (len after TRIPPED)
+    std::uint32_t stop = 0;                // SBE_TERM_APPEND_*
+    std::vector<std::uint64_t> rec_tail;   // [appended] the block offset behind each record
+};
+// required(L): bytes of block the frames of an L-byte record take
+std::uint64_t term_frames_length(std::uint64_t len, std::uint32_t mtu);
+// Records data[rec_off[i], rec_off[i+1]) of a data_len-byte buffer; never reads outside it.
+TermAppendResult term_append(std::uint8_t* block, std::size_t len, std::size_t start, const std::uint8_t* data,
+                             std::size_t data_len, const std::uint64_t* rec_off, std::size_t n,
+                             const TermAppendOptions& options = {});
+class TermAppender {
+public:
+    // Records data[rec_off[i], rec_off[i+1]), i < n, of a data_len-byte host buffer into block[start, len).
+    TermAppendResult append(const std::uint8_t* data, std::size_t data_len, const std::uint64_t* rec_off, std::size_t n,
+                            std::uint8_t* block, std::size_t len, std::size_t start, const TermAppendOptions& options = {});
+    // Records first_record.. of the batch into block[start, len).
+    TermAppendResult append_batch(const EncodedBatch& batch, std::size_t first_record, std::uint8_t* block, std::size_t len,
+                                  std::size_t start, const TermAppendOptions& options = {});
+};
+
 // include/aeron_cluster/order_types.hpp:16-66: the members Order::to_json, Order::validate and
 // publish_order read (the reference class carries more; they play no part in either).
 struct Order {

@@ -150,6 +150,15 @@ class _TermOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("frag_off", "flags", "frag_src", "counts")]
 
 
+class _TermHeader(ctypes.Structure):
+    _fields_ = [("session_id", ctypes.c_int32), ("stream_id", ctypes.c_int32), ("term_id", ctypes.c_int32),
+                ("term_offset_base", ctypes.c_int32), ("version", ctypes.c_uint8)]
+
+
+class _TermAppendOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("rec_tail", "counts")]
+
+
 class _KeyListOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("count", "key", "len", "value", "answered")]
 
@@ -290,6 +299,17 @@ def _load():
     lib.sbe_term_scan.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                   ctypes.c_void_p, ctypes.POINTER(_TermOut), ctypes.c_void_p, ctypes.c_size_t,
                                   ctypes.c_void_p]
+    lib.sbe_term_frames_length.restype = ctypes.c_uint64
+    lib.sbe_term_frames_length.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+    lib.sbe_term_append_workspace_size.restype = ctypes.c_size_t
+    lib.sbe_term_append_workspace_size.argtypes = [ctypes.c_uint64]
+    lib.sbe_term_append_tile.restype = ctypes.c_uint32
+    lib.sbe_term_append_tile.argtypes = []
+    lib.sbe_term_append.restype = ctypes.c_int
+    lib.sbe_term_append.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
+                                    ctypes.POINTER(_TermHeader), ctypes.POINTER(_TermAppendOut), ctypes.c_void_p,
+                                    ctypes.c_size_t, ctypes.c_void_p]
     lib.sbe_inflight_list_workspace_size.restype = ctypes.c_size_t
     lib.sbe_inflight_list_workspace_size.argtypes = [ctypes.c_uint32]
     lib.sbe_inflight_list_keys.restype = ctypes.c_int
@@ -1585,6 +1605,85 @@ def term_scan(block, start=0, limit=None, stream=None, capacity=None, out=None, 
                              _stream(stream))
     _check(rc, "sbe_term_scan")
     return TermFragments(out, frag_off, flags[:capacity], None if frag_src is None else frag_src[:capacity], counts)
+
+
+# sbe_term_append: why the call stopped (counts[3])
+TERM_APPEND_END, TERM_APPEND_LIMIT, TERM_APPEND_TRIPPED, TERM_APPEND_TOO_LONG, TERM_APPEND_BAD_RECORD = range(5)
+TERM_MAX_MESSAGE = 1 << 30
+
+
+@dataclass
+class TermHeader:
+    """The fields every frame header of a term_append call carries; term_offset_base is the term
+    offset of block[0] (the block may be a part of a term)."""
+    session_id: int = 0
+    stream_id: int = 0
+    term_id: int = 0
+    term_offset_base: int = 0
+    version: int = 0
+
+
+@dataclass
+class TermAppended:
+    block: torch.Tensor            # uint8: the block that was appended to
+    rec_tail: torch.Tensor | None  # int64 [n]: the block offset behind record i, i < counts[0]
+    counts: torch.Tensor           # int64 [4]: appended, next (the tail), payload bytes, TERM_APPEND_*
+
+
+def term_append_tile() -> int:
+    """Bytes of block one workgroup of sbe_term_append composes."""
+    return int(lib().sbe_term_append_tile())
+
+
+def term_frames_length(length, mtu=1408) -> int:
+    """Bytes of block the frames of a `length`-byte record take at `mtu`."""
+    if mtu % 32 or not 64 <= mtu <= 65504:
+        raise SbeError("term_frames_length: mtu must be a multiple of 32 in [64, 65504]")
+    return int(lib().sbe_term_frames_length(int(length), int(mtu)))
+
+
+def term_append(block, data, rec_off, start=0, limit=None, mtu=1408, max_message_length=None, header=TermHeader(),
+                stream=None, workspace=None, rec_tail=None, want_tail=True) -> TermAppended:
+    """Appends records data[rec_off[i]:rec_off[i+1]] (an encoder's out / out_off) to the raw
+    term-buffer block from offset `start` with Aeron's framing: one BEGIN|END data frame a record, or
+    BEGIN / middle / END frames of mtu - 32 payload bytes, and a padding-frame header where the block
+    ends before a record fits (counts[3] == TERM_APPEND_TRIPPED: go on with the records from
+    counts[0] in the next term).  block.numel() and start are multiples of 32.  limit: a record is
+    refused once the tail is at or behind it (default: none); max_message_length: default Aeron's
+    rule for a term of block.numel() bytes, min(numel / 8, 16 MiB); rec_tail: an int64 tensor of
+    rec_off.numel() - 1 elements to write the tails to (want_tail=False: none).  data and block
+    must not overlap."""
+    block = _dev(block, torch.uint8, "block")
+    data = _dev(data, torch.uint8, "data")
+    rec_off = _dev(rec_off, torch.int64, "rec_off")
+    nb, n = int(block.numel()), int(rec_off.numel()) - 1
+    dev = block.device
+    start = int(start)
+    if n < 0 or start < 0 or start > nb or (limit is not None and int(limit) < 0):
+        raise SbeError("term_append: rec_off needs an element, start must lie in [0, block.numel()], limit must not be negative")
+    if max_message_length is None:
+        max_message_length = min(nb // 8, 16 << 20)
+    if not want_tail:
+        rec_tail = None
+    elif rec_tail is None:
+        rec_tail = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    elif _dev(rec_tail, torch.int64, "rec_tail").numel() < n:
+        raise SbeError("term_append: rec_tail holds fewer than rec_off.numel() - 1 elements")
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    need = int(lib().sbe_term_append_workspace_size(n))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    h = _TermHeader(int(header.session_id), int(header.stream_id), int(header.term_id), int(header.term_offset_base),
+                    int(header.version))
+    o = _TermAppendOut(None if rec_tail is None else rec_tail.data_ptr(), counts.data_ptr())
+    # an empty tensor has a null data pointer, which the call refuses when there are records (all of
+    # them empty, or none of them fitting): any valid address does, not a byte of it is touched
+    rc = lib().sbe_term_append(_ptr(data if data.numel() else workspace), int(data.numel()), _ptr(rec_off), n,
+                               _ptr(block if nb else workspace), nb, start,
+                               (1 << 64) - 1 if limit is None else int(limit), int(mtu), int(max_message_length),
+                               ctypes.byref(h), ctypes.byref(o), _ptr(workspace), workspace.numel(), _stream(stream))
+    _check(rc, "sbe_term_append")
+    return TermAppended(block, None if rec_tail is None else rec_tail[:n], counts)
 
 
 # bytes per order of the default output bound (a record is at most ~800 B plus its escaped strings:

@@ -89,6 +89,12 @@
  * sbe_term_scan()                 no reference source (third-party Aeron, TermReader::read): the walk
  *                                  over the 32-byte data-frame headers of a term-buffer block that
  *                                  hands fragments to onFragment src/cluster_client.cpp:39-82
+ * sbe_term_append()               no reference source (third-party Aeron, ExclusivePublication::offer ->
+ *                                  ExclusiveTermAppender): the data frames, fragmented at the MTU, and
+ *                                  the end-of-term padding frame that the per-record offer behind
+ *                                  offer_ingress src/cluster_client_offer.cpp:11-20 writes into a term,
+ *                                  for a whole encoded batch (sbe_term_frames_length,
+ *                                  sbe_term_append_workspace_size, sbe_term_append_tile)
  * sbe_inflight_list_keys()        printMessageComparison examples/pubsub_reconnect_test.cpp:130-204 and
  *                                  printClientOrderAudit :206-274: the ids sent and never received, or
  *                                  received and never sent, the first ones in std::set order; with a
@@ -1058,6 +1064,76 @@ uint32_t sbe_term_scan_tile(void);
 int sbe_term_scan(const uint8_t* block, uint64_t block_bytes, uint64_t start, uint64_t fragment_limit,
                   uint64_t frag_capacity, uint8_t* out, const sbe_term_out* o, void* workspace,
                   size_t workspace_bytes, void* stream);
+
+/* The publish side, the mirror of sbe_term_scan: a batch of encoded records (`in`, rec_off[n + 1], as
+ * sbe_encode_session_batch, sbe_publish_orders_batch and sbe_emit_commit_offsets leave them) appended
+ * to a term-buffer block with Aeron's framing, as ExclusivePublication::offer ->
+ * ExclusiveTermAppender::appendUnfragmentedMessage / appendFragmentedMessage /
+ * handleEndOfLogCondition would one record at a time.  Third-party Aeron again: restated from the
+ * data-frame layout above, not pinned to a reference source.  With maxp = mtu - 32 and
+ *   required(L) = L <= maxp ? align(32 + L, 32)
+ *                           : (L / maxp) * mtu + (L % maxp ? align(32 + L % maxp, 32) : 0)
+ * the call is
+ *   tail = start; appended = 0
+ *   for i in 0..n:
+ *       L = rec_off[i+1] - rec_off[i]
+ *       rec_off[i+1] < rec_off[i] or rec_off[i+1] > in_bytes: stop BAD_RECORD
+ *       (this library's own: it never reads outside `in`, whatever the offsets say)
+ *       tail >= limit: stop LIMIT (offer's position < limit test: BACK_PRESSURED)
+ *       L > max_message_length: stop TOO_LONG (checkMaxMessageLength; after the limit, as offer does)
+ *       tail + required(L) > block_bytes:
+ *           if tail < block_bytes: a padding-frame header at tail (frame_length = block_bytes - tail,
+ *           type 0, flags 0xC0, the other fields as a data frame's); tail = block_bytes; stop TRIPPED
+ *           (an exact fit is not a trip; at tail == block_bytes nothing is written)
+ *       the frames of record i at tail; tail += required(L); appended += 1
+ *   stop END when all n went in
+ * A record that stops the call is not consumed: the caller goes on with records[appended:], into the
+ * next term after TRIPPED.  Frames of one record: L <= maxp: one frame, flags 0xC0 (L == 0: 32
+ * bytes); otherwise L / maxp full frames and one for the remainder if there is one, BEGIN (0x80) on the
+ * first, END (0x40) on the last (the last full frame when L % maxp == 0), 0 in between.  Every data-
+ * frame header: frame_length = 32 + payload bytes, hdr->version, the flags, type 1, term_offset =
+ * hdr->term_offset_base + the frame's offset in block (the block may be a part of a term),
+ * hdr->session_id / stream_id / term_id, reserved value 0.
+ * The call writes every byte of [start, tail of the last appended record): headers, payloads and
+ * zeros in each frame's alignment tail (Aeron leaves those to the pre-zeroed term; writing them makes
+ * the block's content a function of the inputs); of a padding frame the 32 header bytes only, as Aeron
+ * does; nothing else in the block and nothing outside it.  There is no ordering between frames (Aeron
+ * commits a frame by writing its length last): this is a batch, not a concurrent publication, and the
+ * block is complete when the call's work on `stream` is.  `in` and block must not overlap (not checked).
+ * Outputs (device memory): counts = {appended, next (the tail), payload bytes appended,
+ * SBE_TERM_APPEND_*}; rec_tail[i] (or NULL) = the block offset behind record i, what offer returns
+ * for it, i < appended (the other elements are written with unspecified values).
+ * SBE_EINVAL (before anything touches a device): null hdr / o / counts; null rec_off / in / block /
+ * workspace when n > 0; block_bytes or start not a multiple of 32; start > block_bytes; block_bytes >
+ * 2^30; mtu not a multiple of 32 or outside [64, 65504]; max_message_length > 2^30; block not 16-B,
+ * rec_off / rec_tail / counts not 8-B aligned; n >= 2^32.  SBE_ENOSPC: n > 0 and workspace_bytes <
+ * sbe_term_append_workspace_size(n).  n == 0: one launch that writes counts (END); otherwise four
+ * launches on `stream` (three when start == block_bytes). */
+#define SBE_TERM_APPEND_END 0u
+#define SBE_TERM_APPEND_LIMIT 1u
+#define SBE_TERM_APPEND_TRIPPED 2u
+#define SBE_TERM_APPEND_TOO_LONG 3u
+#define SBE_TERM_APPEND_BAD_RECORD 4u
+typedef struct sbe_term_header {
+    int32_t session_id;
+    int32_t stream_id;
+    int32_t term_id;
+    int32_t term_offset_base; /* term offset of block[0] */
+    uint8_t version;
+} sbe_term_header;
+typedef struct sbe_term_append_out {
+    uint64_t* rec_tail; /* [n] or NULL: block offset behind record i, i < appended; the rest unspecified */
+    uint64_t* counts;   /* [4] appended, next (tail), payload bytes appended, SBE_TERM_APPEND_* */
+} sbe_term_append_out;
+/* required(L): bytes of block the frames of an L-byte record take; host only, 0 on a bad mtu */
+uint64_t sbe_term_frames_length(uint64_t len, uint32_t mtu);
+size_t sbe_term_append_workspace_size(uint64_t n);
+/* bytes of block one workgroup composes (a multiple of 32) */
+uint32_t sbe_term_append_tile(void);
+int sbe_term_append(const uint8_t* in, uint64_t in_bytes, const uint64_t* rec_off, uint64_t n, uint8_t* block,
+                    uint64_t block_bytes, uint64_t start, uint64_t limit, uint32_t mtu, uint64_t max_message_length,
+                    const sbe_term_header* hdr, const sbe_term_append_out* o, void* workspace, size_t workspace_bytes,
+                    void* stream);
 
 /* ========================== Order JSON (publish_order payload) ========================== */
 /* Replaces Order::to_json (src/order_types.cpp:122-181, jsoncpp StreamWriterBuilder with

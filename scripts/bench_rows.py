@@ -30,6 +30,10 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
                          frames of at most 1376 bytes) framed on the device (sbe_term_scan): the scan alone,
                          tables only, scan + reassembly, a device copy of the payload as the ceiling, and the
                          host mirror's one-thread term_walk with its payload memcpy
+  term_append            the records of that block (built first, encoded in device memory) appended to a 16 MiB
+                         term-buffer block with Aeron's framing at MTU 1408 on the device (sbe_term_append),
+                         a device copy of the same payload bytes as the ceiling, and the host mirror's
+                         one-thread term_append
   ack_correlate          1 M "pub_<nanos>" uuids remembered in a 2 M-slot in-flight table, then 1 M full
                          acks (about 10 % unknown ids, 1 % repeated ids) decoded on-egress and matched;
                          remember, match and the decode of the same ack batch timed in the same run, and
@@ -719,6 +723,81 @@ def row_term_scan(steps, warmup):
     line("term_scan", n, ms_scan * 1e-3, {"sbe_term_scan (3 launches)": (ms_scan, 2 * total + 2 * pbytes + 12 * (total // 32) + 13 * n)})
 
 
+def row_term_append(steps, warmup):
+    """sbe_term_append of the records of the term_scan row (config-3 records, session-framed, every
+    64th a 6 KB TopicMessage) into a 16 MiB term-buffer block at MTU 1408: the records lie encoded in
+    device memory first, the frames are built on the device.  Timed in the same run: the append, a
+    device copy of the same payload bytes (the ceiling), and on the host the mirror's one-thread
+    term_append (tests/termappend/term_append_baseline)."""
+    import subprocess
+    import tempfile
+    import termappend_lib as A
+    total, mtu = 16 << 20, 1408
+    data, off = T.mixed_records(60_000)
+    long_payload = bytes(32 + j % 90 for j in range(6000))
+    recs, used = [], 0
+    for i in range(60_000):
+        rec = bytes(data[int(off[i]):int(off[i + 1])])
+        if i % 64 == 63:
+            rec = T.tm_wire((b"orders", b"CREATE_ORDER", b"msg_%025d" % i, long_payload, b"{}"), 1_760_000_000_000 + i)
+        rec = T.session_wrap(rec)
+        if used + A.required(len(rec), mtu) + 64 > total:
+            break
+        used += A.required(len(rec), mtu)
+        recs.append(rec)
+    n = len(recs)
+    payload, roff = A.pack(recs)
+    pbytes = len(payload)
+    exp = A.append(bytes(total), 0, recs, mtu=mtu, max_message_length=total // 8)
+    assert (exp["appended"], exp["next"], exp["stop"]) == (n, used, A.END)
+    d0 = torch.from_numpy(np.frombuffer(payload, np.uint8).copy()).cuda()
+    o0 = torch.from_numpy(np.asarray(roff, np.int64)).cuda()
+    ws = torch.empty(int(sbecodec.lib().sbe_term_append_workspace_size(n)), dtype=torch.uint8, device="cuda")
+    hdr = sbecodec.TermHeader(7, 1001, 3, 0, 1)
+    R = Rot(lambda k: (d0.clone(), o0.clone(), torch.zeros(total, dtype=torch.uint8, device="cuda"),
+                       torch.empty(n, dtype=torch.int64, device="cuda")))
+    first = sbecodec.term_append(R.sets[0][2], d0, o0, mtu=mtu, header=hdr, workspace=ws)
+    torch.cuda.synchronize()
+    c = first.counts.cpu().numpy()
+    assert (int(c[0]), int(c[1]), int(c[2]), int(c[3])) == (n, used, pbytes, A.END), c
+    assert first.block[:used].cpu().numpy().tobytes() == exp["block"][:used]
+    assert first.rec_tail.cpu().numpy().tolist() == exp["rec_tail"]
+
+    def append():
+        d, o, blk, tails = R.next()
+        sbecodec.term_append(blk, d, o, mtu=mtu, header=hdr, workspace=ws, rec_tail=tails)
+
+    def copy():
+        d, _, blk, _ = R.next()
+        blk[:pbytes].copy_(d)
+
+    ms_app, ms_copy = (_event_ms(f, steps, warmup) for f in (append, copy))
+    # the payload read, [start, next) written, rec_off read by three of the launches, the tails written and read
+    nbytes = pbytes + used + 3 * 8 * (n + 1) + 2 * 8 * n
+    extra = {"row": "term_append_detail", "block_bytes": total, "records": n, "payload_bytes": pbytes, "written_bytes": used,
+             "frames": sum(max(1, -(-len(r) // (mtu - 32))) for r in recs), "append_ms": ms_app, "device_copy_ms": ms_copy,
+             "counted_bytes": nbytes, "append_GBps": nbytes / (ms_app * 1e-3) / 1e9,
+             "copy_GBps": 2 * pbytes / (ms_copy * 1e-3) / 1e9,
+             "launches": "ta_sums, ta_scan_blocks, ta_tails, ta_write", "tile_bytes": sbecodec.term_append_tile(),
+             "tiles": -(-used // sbecodec.term_append_tile())}
+    if not NO_CPU:
+        dd = os.path.join(ROOT, "tests", "termappend")
+        subprocess.run(["make", "-s", "-C", dd, "term_append_baseline"], check=True)
+        with tempfile.NamedTemporaryFile(suffix=".bin") as tf:
+            tf.write(np.asarray([n] + roff, np.uint64).tobytes())
+            tf.write(payload)
+            tf.flush()
+            cpu = json.loads(subprocess.run([os.path.join(dd, "term_append_baseline"), tf.name, str(total)], check=True,
+                                            capture_output=True, text=True).stdout)
+        assert (cpu["appended"], cpu["next"], cpu["stop"]) == (n, used, A.END), cpu
+        extra["host_term_append_ms"] = cpu["term_append_ms"]
+        extra["host_over_device"] = cpu["term_append_ms"] / ms_app
+        set_cpu(n / (cpu["term_append_ms"] * 1e-3), "the same records, host mirror term_append, 1 thread (one publication "
+                "appends serially)", cores=1)
+    print(json.dumps(extra), flush=True)
+    line("term_append", n, ms_app * 1e-3, {"sbe_term_append (4 launches)": (ms_app, nbytes)})
+
+
 def row_commit_emit(steps, warmup):
     """sbe_emit_commit_offsets over 1 M decoded and classified fixed-256 Orders whose headers all
     carry a known topic (every record emits a session-framed CommitOffsetLite; short identifiers),
@@ -1148,7 +1227,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,order_select,term_scan,commit_emit,commit_fallback,ack_correlate,delivery_track,delivery_report")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,order_select,term_scan,term_append,commit_emit,commit_fallback,ack_correlate,delivery_track,delivery_report")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -1183,6 +1262,8 @@ def main():
             row_order_select(args.steps, args.warmup)
         elif r == "term_scan":
             row_term_scan(args.steps, args.warmup)
+        elif r == "term_append":
+            row_term_append(args.steps, args.warmup)
         elif r == "commit_emit":
             row_commit_emit(args.steps, args.warmup)
         elif r == "commit_fallback":
