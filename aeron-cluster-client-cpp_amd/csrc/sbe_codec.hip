@@ -324,6 +324,20 @@ constexpr int kSinkBytes = 16 * 64;
 // Cache policy of the pack kernel's output stores (buffer stores; 2 = nt: the stream is written
 // once and read by the next kernel or the host, not from this kernel's caches)
 constexpr int kOutAux = 2;
+// ... except where the whole stream fits the 256 MiB Infinity Cache: default-policy stores leave it
+// there for the kernel that reads it next (nontemporal stores do not), and the tile loop of a batch
+// whose estimated stream lies in [kKeepMin, kKeepMax] takes them (keep_pays; the virtual-tile loop,
+// the one session frames and config 4 take, keeps nt).  Rotated inputs, builds interleaved in one
+// process, fixed-256 round trip nt / keep: 1 M records step 156.7 / 152.2 us (decode 55.9 / 50.6, pack
+// 95.2 / 94.1); 750 k 124.2 / 122.2; 500 k 90.7 / 88.6; 250 k 54.7 / 54.5 (pack 30.4 / 31.1, decode
+// 19.2 / 18.2: below ~100 MB the decode's gain no longer covers the pack's cost; CommitOffsetLite,
+// 75 MB, pack 44.3 / 45.7, decode equal).  Keep for every batch: 1.5 M 226.1 / 224.0, 2 M 293.6 /
+// 292.2, but session frames 220.5 / 227.0 (wide-window decode 64.3 / 71.4) and config 4's pack 714 /
+// 727.  As a branch inside store_rows (one kernel body) the pack of a 2 M batch read 180.9 -> 183.2
+// with the branch not taken, so the policy is a template argument of the tile loop
+// (profiles/r24_final_ab_rot3.log, r24_ab_keep_size_sweep.log, r24_ab_policy_rows_rot3.log).
+constexpr int kOutAuxKeep = 0;
+constexpr uint64_t kKeepMin = 96ull << 20, kKeepMax = 256ull << 20;
 
 // Record length modes of the TopicMessage encoders:
 //   kLenWire  the wire record, 34+Σlen (computeLength's E109 above 65534 B)
@@ -925,7 +939,7 @@ __device__ __forceinline__ void compose(const EncArgs& a, lds_u8* wout, lds_cu8*
 // full; layouts of small records whose 32-record tiles are a few KiB (CommitOffsetLite) skip the
 // empty rows: the join after the branch makes the compiler wait for the longer path's extra stores
 // before the next window's staging, but the short path, the one those tiles take, waits exactly.
-template <int kRows0>
+template <int kRows0, int kAux>
 __device__ __forceinline__ void store_rows(uint8_t* out, lds_cu8* wout, uint64_t wb, uint64_t lo, uint64_t we,
                                            uint32_t nch, uint32_t c_lo, uint32_t c_hi,
                                            const __amdgpu_buffer_rsrc_t& rs, int lane, int k0) {
@@ -937,14 +951,14 @@ __device__ __forceinline__ void store_rows(uint8_t* out, lds_cu8* wout, uint64_t
         v[k] = make_uint4(a0.x, a0.y, a0.z, a0.w);
     }
     // unconditional 16-byte buffer stores; chunks not wholly inside [lo, we) take an offset past
-    // the descriptor's range, which the hardware drops (cache policy kOutAux)
+    // the descriptor's range, which the hardware drops (cache policy kAux: kOutAux or kOutAuxKeep)
 #pragma unroll
     for (int k = 0; k < kRows0; ++k) {
         const uint32_t ch = lane + kWave * (k0 + k);
         const bool full = ch >= c_lo && ch < c_hi;
         u32x4 x;
         x.x = v[k].x; x.y = v[k].y; x.z = v[k].z; x.w = v[k].w;
-        __builtin_amdgcn_raw_buffer_store_b128(x, rs, full ? (int)(16u * ch) : 0x7ffffff0, 0, kOutAux);
+        __builtin_amdgcn_raw_buffer_store_b128(x, rs, full ? (int)(16u * ch) : 0x7ffffff0, 0, kAux);
     }
 }
 
@@ -991,7 +1005,7 @@ __device__ __forceinline__ void store_edges(uint8_t* out, lds_cu8* wout, uint64_
 }
 
 constexpr int kStoreRows = kEW / 16 / kWave;  // rows of 64 chunks in a window
-template <int kRows0 = kStoreRows>
+template <int kRows0 = kStoreRows, int kAux = kOutAux>
 __device__ __forceinline__ void store_window(uint8_t* out, lds_cu8* wout, uint64_t T0, uint64_t wb, uint64_t we,
                                              int lane) {
     static_assert(kRows0 >= 1 && kRows0 <= kStoreRows, "store rows");
@@ -1000,10 +1014,10 @@ __device__ __forceinline__ void store_window(uint8_t* out, lds_cu8* wout, uint64
     const uint32_t c_lo = (uint32_t)((lo - wb + 15) >> 4);  // chunks [c_lo, c_hi) lie inside [lo, we)
     const uint32_t c_hi = (uint32_t)((we - wb) >> 4);
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(out + wb, 0, (int)(16u * c_hi), 0x00020000);
-    store_rows<kRows0>(out, wout, wb, lo, we, nch, c_lo, c_hi, rs, lane, 0);
+    store_rows<kRows0, kAux>(out, wout, wb, lo, we, nch, c_lo, c_hi, rs, lane, 0);
     if constexpr (kRows0 < kStoreRows) {
         if (nch > (uint32_t)(kWave * kRows0))
-            store_rows<kStoreRows - kRows0>(out, wout, wb, lo, we, nch, c_lo, c_hi, rs, lane, kRows0);
+            store_rows<kStoreRows - kRows0, kAux>(out, wout, wb, lo, we, nch, c_lo, c_hi, rs, lane, kRows0);
     }
     store_edges(out, wout, wb, lo, we, c_lo, c_hi, lane);
 }
@@ -1784,10 +1798,12 @@ struct PackLds {
 };
 
 // Tiles first, first + G, ... of the batch (the pack kernel: first = blockIdx.x, G = gridDim.x;
-// the serve kernel: 0, 1 for a one-tile batch).
-template <class LY, bool kPacked, int kLen>
+// the serve kernel: 0, 1 for a one-tile batch).  kKeep: the stream stays in the Infinity Cache for the
+// kernel that reads it next (keep_pays).
+template <class LY, bool kPacked, int kLen, bool kKeep = false>
 __device__ __forceinline__ void enc_pack_run(const EncArgs& a, uint64_t first, uint64_t G, PackLds<LY, kPacked>& L) {
     SBE_TILE_SHAPE(LY);
+    constexpr int kAux = kKeep ? kOutAuxKeep : kOutAux;
     lds_u8* const wout = (lds_u8*)L.wout;
     lds_u8* const win_in = (lds_u8*)L.win + kInSlack;
     lds_i32* const rt = (lds_i32*)L.rt;
@@ -1847,7 +1863,7 @@ __device__ __forceinline__ void enc_pack_run(const EncArgs& a, uint64_t first, u
                 ph.lap(3);
             }
             wsync();
-            store_window<(LY::kStoreRows0 < kStoreRows ? LY::kStoreRows0 : kStoreRows)>(a.out, wout, S.T0 + W.A, S.T0 + (int64_t)W.wrel,
+            store_window<(LY::kStoreRows0 < kStoreRows ? LY::kStoreRows0 : kStoreRows), kAux>(a.out, wout, S.T0 + W.A, S.T0 + (int64_t)W.wrel,
                                           S.T0 + (int64_t)(W.wrel + W.wlen), lane);
             wsync();
             ph.lap(4);
@@ -1881,7 +1897,7 @@ __device__ __forceinline__ void enc_pack_run(const EncArgs& a, uint64_t first, u
                     compose<LY, false>(a, wout, win_in, S, wrel, we_rel, sw, nbw);
                 }
                 wsync();
-                store_window(a.out, wout, S.T0, S.T0 + (int64_t)wrel, S.T0 + (uint64_t)we_rel, lane);
+                store_window<kStoreRows, kAux>(a.out, wout, S.T0, S.T0 + (int64_t)wrel, S.T0 + (uint64_t)we_rel, lane);
                 wsync();
             }
             ph.lap(6);
@@ -1961,6 +1977,7 @@ template <class LY, bool kPacked, int kLen>
 __device__ __forceinline__ void enc_pack_run_vt(const EncArgs& a, uint64_t first, uint64_t G, PackLds<LY, kPacked>& L,
                                                 bool spread = false) {
     SBE_TILE_SHAPE(LY);
+    constexpr int kAux = kOutAux;
     lds_u8* const wout = (lds_u8*)L.wout;
     lds_u8* const win_in = (lds_u8*)L.win + kInSlack;
     lds_i32* const rt = (lds_i32*)L.rt;
@@ -2099,7 +2116,7 @@ __device__ __forceinline__ void enc_pack_run_vt(const EncArgs& a, uint64_t first
                 ph.lap(3);
             }
             wsync();
-            store_window<(LY::kStoreRows0 < kStoreRows ? LY::kStoreRows0 : kStoreRows)>(a.out, wout, S.T0 + W.A, S.T0 + (int64_t)W.wrel,
+            store_window<(LY::kStoreRows0 < kStoreRows ? LY::kStoreRows0 : kStoreRows), kAux>(a.out, wout, S.T0 + W.A, S.T0 + (int64_t)W.wrel,
                                           S.T0 + (int64_t)(W.wrel + W.wlen), lane);
             wsync();
             ph.lap(4);
@@ -2135,7 +2152,7 @@ __device__ __forceinline__ void enc_pack_run_vt(const EncArgs& a, uint64_t first
                     compose<LY, false>(a, wout, win_in, S, wrel, we_rel, sw, nbw);
                 }
                 wsync();
-                store_window(a.out, wout, S.T0, S.T0 + (int64_t)wrel, S.T0 + (uint64_t)we_rel, lane);
+                store_window<kStoreRows, kAux>(a.out, wout, S.T0, S.T0 + (int64_t)wrel, S.T0 + (uint64_t)we_rel, lane);
                 wsync();
             }
             ph.lap(6);
@@ -2182,11 +2199,23 @@ __device__ __forceinline__ bool vt_pays(const EncArgs& a) {
     const uint64_t last = t - (t - 1) / kEW * kEW;        // bytes in the tile's last window
     return 10 * last < 6 * (uint64_t)kEW;
 }
+// The stream's size, estimated from the first superblock's average record (the same uniform read
+// as vt_pays, the same choice in every workgroup), against [kKeepMin, kKeepMax] (kOutAuxKeep).  The policy
+// changes no byte of the output, so an estimate is enough.
+template <class LY>
+__device__ __forceinline__ bool keep_pays(const EncArgs& a) {
+    SBE_TILE_SHAPE(LY);
+    const uint64_t n0 = a.n < (uint64_t)kSbRec ? a.n : (uint64_t)kSbRec;
+    const uint64_t est = uniform64(a.bsum[0]) * a.n / n0;
+    return est >= kKeepMin && est <= kKeepMax;
+}
 template <class LY, bool kPacked, int kLen>
 __global__ __launch_bounds__(kWave, SBE_PACK_MIN_WAVES) void sbe_enc_pack(EncArgs a) {
     __shared__ PackLds<LY, kPacked> lds;
     if (kPacked && vt_pays<LY>(a))
         enc_pack_run_vt<LY, kPacked, kLen>(a, blockIdx.x, gridDim.x, lds);
+    else if (keep_pays<LY>(a))
+        enc_pack_run<LY, kPacked, kLen, true>(a, blockIdx.x, gridDim.x, lds);
     else
         enc_pack_run<LY, kPacked, kLen>(a, blockIdx.x, gridDim.x, lds);
 }
@@ -2853,7 +2882,10 @@ __device__ __noinline__ Desc dec_record_glb(const uint8_t* in, uint64_t rs, uint
 // The decode's staging loads are nontemporal (the records are read once): against the default cache
 // policy, rotated inputs, fixed-256 55.4 / 57.2 us, config 3 58.5 / 59.6, session frames 63.4 /
 // 65.6, OrderRequestLite 66.5 / 71.0; one set re-read, fixed-256 56.3 / 58.4, config 4 410.9 / 430.9
-// (profiles/r06_ab_decntl_{rot,warm}.log)
+// (profiles/r06_ab_decntl_{rot,warm}.log); with the stream left in the Infinity Cache by the pack
+// (kOutAuxKeep) still 154.5 / 157.5 us a round trip, and the descriptor stores (dst_store), nontemporal
+// as well, 154.5 / 154.7 there and 158.2 / 162.6 behind nontemporal pack stores
+// (profiles/r24_ab_policy_matrix_rot3.log)
 template <uint32_t kW>
 __device__ __forceinline__ void dec_issue(const DecArgs& a, uint64_t wb, uint64_t we, int lane,
                                           uint4 (&I)[dec_regs<kW>()]) {
@@ -3118,6 +3150,10 @@ template <uint32_t kMode, uint32_t kWin>
 // the 20 KiB window's LDS allows 8 workgroups per CU, 2 waves per SIMD: its registers are sized for that
 __global__ __launch_bounds__(kWave, kWin == kWinWide && kWinWide > 16384 ? 2 : ((kWin == kWinWide || kWin == kWinLarge) ? SBE_DEC_MINW_WIDE : SBE_DEC_MINW)) void sbe_decode_kernel(DecArgs a) {
     __shared__ uint32_t win[kWin / 4];
+    // Tiles in stream order.  Newest-first (tile gridDim.x - 1 - blockIdx.x, to start at the lines the
+    // producer wrote last) read 158.2 against 157.1 us a round trip behind nontemporal pack stores and
+    // 153.0 against 152.0 behind default-policy ones, about 1 us behind at every batch size from 250 k
+    // to 2 M records (profiles/r24_ab_policy_matrix_rot3.log, r24_ab_keep_size_sweep.log).
     dec_tile<kMode, kWin>(a, blockIdx.x, win);
 }
 
