@@ -3378,18 +3378,21 @@ __device__ __forceinline__ FragScan fs_block(const FragArgs& a, uint64_t b, Frag
     before = FragScanOp{}(wpre, ex);
     return tot;
 }
-__global__ __launch_bounds__(kFsThreads) void frag_reduce(FragArgs a, FragScan* agg) {
+// The three scan launches' bodies are functions of their own: sbe_term_poll (term_poll.hpp) runs
+// them from kernels that read the fragment count from device memory first.
+__device__ __forceinline__ void frag_reduce_body(const FragArgs& a, FragScan* agg) {
     __shared__ FragScan wt[kFsThreads / kWave];
     const uint64_t b = blockIdx.x;
     FragScan e[kFsPer], before;
     const FragScan tot = fs_block(a, b, e, wt, before);
     if (threadIdx.x == 0) agg[b] = tot;
 }
+__global__ __launch_bounds__(kFsThreads) void frag_reduce(FragArgs a, FragScan* agg) { frag_reduce_body(a, agg); }
 // exclusive prefixes of the nb block aggregates, in place: one workgroup of kFsThreads threads,
 // kFsPer consecutive aggregates a thread (a million fragments' 977 aggregates in one pass; at 1024
 // threads a pass the scan's registers spilled: 21 us instead of a few)
 constexpr int kFsbThreads = kFsThreads;
-__global__ __launch_bounds__(kFsbThreads) void frag_scan_blocks(FragScan* agg, uint64_t nb, uint64_t* big) {
+__device__ __forceinline__ void frag_scan_blocks_body(FragScan* agg, uint64_t nb, uint64_t* big) {
     __shared__ FragScan wt[kFsbThreads / kWave];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
     if (big && tid == 0) big[0] = 0;  // the big-message list of frag_scan_msgs (next launch)
@@ -3421,6 +3424,9 @@ __global__ __launch_bounds__(kFsbThreads) void frag_scan_blocks(FragScan* agg, u
             if (j0 + k < nb) agg[j0 + k] = k ? FragScanOp{}(P, r[k - 1]) : P;
         carry = FragScanOp{}(carry, tot);
     }
+}
+__global__ __launch_bounds__(kFsbThreads) void frag_scan_blocks(FragScan* agg, uint64_t nb, uint64_t* big) {
+    frag_scan_blocks_body(agg, nb, big);
 }
 
 // frag_scan_msgs: the third scan launch and the message table in one.  The block's inclusive scan
@@ -3465,7 +3471,7 @@ __device__ __noinline__ uint32_t frag_singles_before(const FragArgs& a, const Fr
     return fwd ? c + cnt : c - cnt;
 }
 
-__global__ __launch_bounds__(kFsThreads) void frag_scan_msgs(FragArgs a, const FragScan* pre) {
+__device__ __forceinline__ void frag_scan_msgs_body(const FragArgs& a, const FragScan* pre) {
     __shared__ FragScan wt[kFsThreads / kWave];
     __shared__ uint32_t sgl[kFsBlk];  // inclusive singles count at every fragment of the block
     __shared__ uint64_t stg[kFsBlk];  // one table array of the block's messages
@@ -3555,6 +3561,9 @@ __global__ __launch_bounds__(kFsThreads) void frag_scan_msgs(FragArgs a, const F
         for (uint32_t t = tid; t < nj; t += kFsThreads) dst[t] = stg[t];
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(kFsThreads) void frag_scan_msgs(FragArgs a, const FragScan* pre) {
+    frag_scan_msgs_body(a, pre);
 }
 
 // wave copy of src[0, len) to dst with 16-byte nontemporal stores once dst is aligned; four chunks
@@ -4411,6 +4420,7 @@ __global__ __launch_bounds__(kWave, 1) void sbe_serve_kernel(ServeSlot* slot, ui
 #include "delivery_report.hpp"
 #include "order_select.hpp"
 #include "term_scan.hpp"
+#include "term_poll.hpp"
 #include "term_append.hpp"
 
 }  // namespace
@@ -5528,6 +5538,92 @@ int sbe_term_scan(const uint8_t* block, uint64_t block_bytes, uint64_t start, ui
     hipLaunchKernelGGL(term_tile_chain, dim3(nt), dim3(kTsSlots), 0, s, a, tile0);
     hipLaunchKernelGGL(term_walk_tiles, dim3(1), dim3(kWave), 0, s, a);
     hipLaunchKernelGGL(term_emit, dim3(nt), dim3(kTsSlots), 0, s, a);
+    return record_hip(hipGetLastError());
+}
+
+// entries of sbe_term_poll's fragment tables: a fragment takes a slot at least, and the carry leads
+static uint64_t tp_table_entries(uint64_t block_bytes, uint64_t frag_capacity) {
+    const uint64_t slots = block_bytes / 32;
+    return (frag_capacity < slots ? frag_capacity : slots) + 1;
+}
+
+size_t sbe_term_poll_workspace_size(uint64_t block_bytes, uint64_t frag_capacity) {
+    // the scan's workspace; frag_off / flags / frag_src; block aggregates; sizes, first / last
+    // fragment per message; each piece on 16 bytes
+    const uint64_t n = tp_table_entries(block_bytes, frag_capacity), nb = (n + kFsBlk - 1) / kFsBlk;
+    return sbe_term_scan_workspace_size(block_bytes) +
+           (size_t)(8 * (n + 1) + (n + 16) + 4 * n + (nb + 1) * sizeof(FragScan) + 3 * 8 * (n + 1) + 7 * 16);
+}
+
+int sbe_term_poll(const uint8_t* block, uint64_t block_bytes, uint64_t start, uint64_t fragment_limit,
+                  uint64_t frag_capacity, const uint8_t* carry, uint64_t carry_bytes, uint8_t* out,
+                  uint64_t out_capacity, const sbe_term_poll_out* o, void* workspace, size_t workspace_bytes,
+                  void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!o || !o->counts || !o->msg_off || !out) return SBE_EINVAL;
+    if ((block_bytes & 31) || (start & 31) || start > block_bytes || block_bytes > kTsMaxBlock) return SBE_EINVAL;
+    if (misaligned(block, 15) || misaligned(o->msg_off, 7) || misaligned(o->counts, 7)) return SBE_EINVAL;
+    if (block_bytes > start && (!block || !workspace)) return SBE_EINVAL;
+    if (carry_bytes > 0 && !carry) return SBE_EINVAL;
+    if (carry_bytes > (1ull << 31) || carry_bytes + (block_bytes - start) > (1ull << 31)) return SBE_EINVAL;
+    if (carry_bytes > 0 && out_capacity > 0) {  // the carry is read while out is written
+        const uintptr_t c0 = reinterpret_cast<uintptr_t>(carry), o0 = reinterpret_cast<uintptr_t>(out);
+        if (c0 < o0 + out_capacity && o0 < c0 + carry_bytes) return SBE_EINVAL;
+    }
+    const uint64_t bound = carry_bytes + (block_bytes - start);
+    if (out_capacity < bound) return SBE_ENOSPC;
+    if (block_bytes > start && workspace_bytes < sbe_term_poll_workspace_size(block_bytes, frag_capacity))
+        return SBE_ENOSPC;
+    const uint64_t limit = fragment_limit < frag_capacity ? fragment_limit : frag_capacity;
+    if (limit == 0 || block_bytes == start) {
+        hipLaunchKernelGGL(tp_counts_only, dim3(1), dim3(1), 0, s, o->counts, o->msg_off, start,
+                           limit == 0 ? SBE_TERM_STOP_LIMIT : SBE_TERM_STOP_END, carry_bytes);
+        if (carry_bytes)
+            hipLaunchKernelGGL(tp_copy_carry, dim3((uint32_t)((carry_bytes + kTpWaves * kTpPiece - 1) / (kTpWaves * kTpPiece))),
+                               dim3(kTpWaves * kWave), 0, s, out, carry, carry_bytes);
+        return record_hip(hipGetLastError());
+    }
+    const uint64_t tiles = (block_bytes + kTsTileBytes - 1) / kTsTileBytes;
+    const uint32_t tile0 = (uint32_t)(start / kTsTileBytes), nt = (uint32_t)tiles - tile0;
+    const uint32_t lead = carry_bytes ? 1u : 0u;
+    const uint64_t n = tp_table_entries(block_bytes, frag_capacity), nb = (n + kFsBlk - 1) / kFsBlk;
+    Carver ws(workspace);
+    TsArgs t{block, block_bytes, start, limit, nullptr, nullptr, nullptr, nullptr, o->counts};
+    t.w_exit = ws.take<uint32_t>(tiles * kTsSlots);
+    t.w_frags = ws.take<uint32_t>(tiles * kTsSlots);
+    t.w_bytes = ws.take<uint32_t>(tiles * kTsSlots);
+    t.visited = ws.take<uint4>(tiles);
+    t.nvisited = ws.take<uint32_t>(1);
+    uint64_t* frag_off = ws.take<uint64_t>(n + 1);
+    uint8_t* flags = ws.take<uint8_t>(n + 16);  // frag_singles_before reads whole aligned 16-byte blocks
+    uint32_t* frag_src = ws.take<uint32_t>(n);
+    FragScan* el = ws.take<FragScan>(nb + 1);
+    uint64_t* msize = ws.take<uint64_t>(n + 1);
+    uint64_t* mfirst = ws.take<uint64_t>(n + 1);
+    uint64_t* mlast = ws.take<uint64_t>(n + 1);
+    // the walk's tables behind the carry's entry
+    t.frag_off = frag_off + lead;
+    t.flags = flags + lead;
+    t.frag_src = frag_src + lead;
+    if (lead)
+        hipLaunchKernelGGL(tp_carry_entry, dim3(1), dim3(1), 0, s, reinterpret_cast<int64_t*>(frag_off), flags, frag_src,
+                           carry_bytes);
+    hipLaunchKernelGGL(term_tile_chain, dim3(nt), dim3(kTsSlots), 0, s, t, tile0);
+    hipLaunchKernelGGL(term_walk_tiles, dim3(1), dim3(kWave), 0, s, t);
+    hipLaunchKernelGGL(term_emit, dim3(nt), dim3(kTsSlots), 0, s, t);
+    // the fragments the walk can deliver from here bound the grids; the count itself stays on the device
+    const uint64_t slots = (block_bytes - start) / 32;
+    const uint64_t nmax = (limit < slots ? limit : slots) + lead;
+    const uint32_t gb = (uint32_t)((nmax + kFsBlk - 1) / kFsBlk);
+    FragArgs a{nullptr, frag_off, flags, 0, out, o->msg_off, o->counts + 4, el, nullptr, msize, mfirst, mlast, nullptr};
+    const uint64_t* cnt = o->counts;
+    hipLaunchKernelGGL(tp_frag_reduce, dim3(gb), dim3(kFsThreads), 0, s, a, el, cnt, lead);
+    hipLaunchKernelGGL(tp_frag_scan_blocks, dim3(1), dim3(kFsbThreads), 0, s, el, cnt, lead, o->msg_off, o->counts + 4);
+    hipLaunchKernelGGL(tp_frag_scan_msgs, dim3(gb), dim3(kFsThreads), 0, s, a, static_cast<const FragScan*>(el), cnt, lead);
+    TpArgs g{block, carry, out, frag_src,
+             TpTables{reinterpret_cast<const int64_t*>(frag_off), flags, o->msg_off, msize, mfirst, mlast, 0}, cnt};
+    const uint64_t pieces = (bound + kTpPiece - 1) / kTpPiece;
+    hipLaunchKernelGGL(term_poll_gather, dim3((uint32_t)((pieces + kTpWaves - 1) / kTpWaves)), dim3(kTpWaves * kWave), 0, s, g);
     return record_hip(hipGetLastError());
 }
 

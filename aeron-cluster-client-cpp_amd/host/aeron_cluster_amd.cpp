@@ -3100,6 +3100,52 @@ EncodedBatch FragmentReassembler::on_term_block(const std::uint8_t* block, std::
     return b;
 }
 
+EncodedBatch FragmentReassembler::poll_term_block(const std::uint8_t* block, std::size_t len, std::size_t start,
+                                                  std::size_t limit, std::size_t* next) {
+    if ((len & 31) || (start & 31) || start > len) throw std::invalid_argument("poll_term_block: block and start are multiples of 32");
+    Ctx& c = ctx();
+    Pipeline::Slot& s = c.pipe.slot[0];  // as on_fragments
+    hipStream_t stream = c.batch_stream();
+    const size_t body = len - start, carry_in = acc_.size(), bound = carry_in + body;
+    if (body > ((size_t)1 << 30) || bound > ((size_t)1 << 31)) throw std::invalid_argument("poll_term_block: more than 2^30 bytes");
+    const uint64_t lim = limit == ~(size_t)0 ? ~0ull : (uint64_t)limit;
+    const uint64_t cap = lim < body / 32 ? lim : body / 32;
+    // the block as it is, the accumulator behind it (the call reads it from there as its carry)
+    const size_t i_carry = al16(body);
+    s.d_in.need(i_carry + carry_in + 16);
+    if (body) hip_check(hipMemcpyAsync(s.d_in.p, block + start, body, hipMemcpyHostToDevice, stream), "H2D");
+    if (carry_in) hip_check(hipMemcpyAsync(s.d_in.b() + i_carry, acc_.data(), carry_in, hipMemcpyHostToDevice, stream), "H2D");
+    const size_t o_off = al16(bound), o_cnt = o_off + (cap + 1) * 8, o_ws = al16(o_cnt + 48);
+    const size_t wsb = sbe_term_poll_workspace_size(body, cap);
+    s.d_out.need(o_ws + wsb + 16);
+    uint8_t* dout = s.d_out.b();
+    const sbe_term_poll_out po{reinterpret_cast<uint64_t*>(dout + o_off), reinterpret_cast<uint64_t*>(dout + o_cnt)};
+    if (sbe_term_poll(s.d_in.b(), body, 0, lim, cap, carry_in ? s.d_in.b() + i_carry : nullptr, carry_in, dout, bound, &po,
+                      dout + o_ws, wsb, stream) != SBE_OK)
+        fail("sbe_term_poll");
+    c.h_aux.need(48);
+    uint64_t* counts = reinterpret_cast<uint64_t*>(c.h_aux.p);
+    hip_check(hipMemcpyAsync(counts, po.counts, 48, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");  // the call's one wait: the rest are the downloads
+    if (next) *next = start + (size_t)counts[1];
+    const uint64_t m = counts[4], carry = counts[5];
+    EncodedBatch b;
+    b.offsets = HostBytesAccess::make<uint64_t>(m + 1);
+    b.offsets[0] = 0;
+    if (counts[0] == 0) return b;  // no fragment: nothing delivered, the accumulator as it was
+    b.status = HostBytesAccess::make<uint8_t>(m);
+    HostBytesAccess::zero(b.status);
+    hip_check(hipMemcpyAsync(b.offsets.data(), po.msg_off, (m + 1) * 8, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    const uint64_t msg_bytes = b.offsets[m];
+    b.bytes = HostBytesAccess::make((size_t)msg_bytes);
+    acc_.resize(carry);
+    if (msg_bytes) hip_check(hipMemcpyAsync(b.bytes.data(), dout, msg_bytes, hipMemcpyDeviceToHost, stream), "D2H");
+    if (carry) hip_check(hipMemcpyAsync(acc_.data(), dout + msg_bytes, carry, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    return b;
+}
+
 TermAppendResult TermAppender::append_batch(const EncodedBatch& batch, std::size_t first_record, std::uint8_t* block,
                                             std::size_t len, std::size_t start, const TermAppendOptions& options) {
     const size_t total = batch.offsets.size() ? batch.offsets.size() - 1 : 0;

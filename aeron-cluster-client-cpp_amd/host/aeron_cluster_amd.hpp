@@ -889,6 +889,14 @@ public:
     // walk stopped (the start of the next call).  The carry is kept exactly as on_fragments keeps it.
     EncodedBatch on_term_block(const std::uint8_t* block, std::size_t len, std::size_t start, std::size_t limit,
                                std::size_t* next = nullptr);
+    // The same result, *next and kept carry as on_term_block for every input, through the one call
+    // sbe_term_poll: the block goes to the device once and unshifted, the accumulator goes up as the
+    // call's carry, and the host waits once for the six counts before the downloads (on_term_block
+    // waits for the scan's counts, the reassembly's counts and the offsets one after another).
+    // std::invalid_argument also when block[start, len) exceeds 2^30 bytes or, with the accumulator,
+    // 2^31.
+    EncodedBatch poll_term_block(const std::uint8_t* block, std::size_t len, std::size_t start, std::size_t limit,
+                                 std::size_t* next = nullptr);
     std::size_t pending_bytes() const { return acc_.size(); }
 
 private:

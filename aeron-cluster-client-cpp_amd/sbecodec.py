@@ -150,6 +150,10 @@ class _TermOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("frag_off", "flags", "frag_src", "counts")]
 
 
+class _TermPollOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("msg_off", "counts")]
+
+
 class _TermHeader(ctypes.Structure):
     _fields_ = [("session_id", ctypes.c_int32), ("stream_id", ctypes.c_int32), ("term_id", ctypes.c_int32),
                 ("term_offset_base", ctypes.c_int32), ("version", ctypes.c_uint8)]
@@ -299,6 +303,12 @@ def _load():
     lib.sbe_term_scan.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                   ctypes.c_void_p, ctypes.POINTER(_TermOut), ctypes.c_void_p, ctypes.c_size_t,
                                   ctypes.c_void_p]
+    lib.sbe_term_poll_workspace_size.restype = ctypes.c_size_t
+    lib.sbe_term_poll_workspace_size.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    lib.sbe_term_poll.restype = ctypes.c_int
+    lib.sbe_term_poll.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                  ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                  ctypes.POINTER(_TermPollOut), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.sbe_term_frames_length.restype = ctypes.c_uint64
     lib.sbe_term_frames_length.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
     lib.sbe_term_append_workspace_size.restype = ctypes.c_size_t
@@ -1605,6 +1615,69 @@ def term_scan(block, start=0, limit=None, stream=None, capacity=None, out=None, 
                              _stream(stream))
     _check(rc, "sbe_term_scan")
     return TermFragments(out, frag_off, flags[:capacity], None if frag_src is None else frag_src[:capacity], counts)
+
+
+@dataclass
+class TermMessages:
+    out: torch.Tensor      # uint8: the messages back to back, then the open accumulator (the carry)
+    msg_off: torch.Tensor  # int64 [capacity + 1]: message j = out[msg_off[j]:msg_off[j+1]] for j < m
+    counts: torch.Tensor   # int64 [6]: fragments, next, payload bytes, TERM_STOP_*, m, carry bytes
+
+
+def term_poll(block, start=0, limit=None, carry=None, capacity=None, out=None, msg_off=None, workspace=None,
+              stream=None) -> TermMessages:
+    """term_scan and reassemble in one call: the whole messages a poll of one image finds in a raw
+    term-buffer block from offset `start`, at most `limit` fragments.  carry: the open accumulator of
+    the poll before (uint8 device tensor, e.g. a view out[msg_off[m]:msg_off[m] + counts[5]] of that
+    call's result; it must not overlap this call's out, so two out buffers alternate).  The carry
+    after this call is out[msg_off[m]:msg_off[m] + counts[5]] with m = counts[4].  capacity and limit
+    default as in term_scan; out holds carry.numel() + block.numel() - start bytes, msg_off
+    capacity + 1 entries.  Nothing is read back: the counts stay on the device."""
+    block = _dev(block, torch.uint8, "block")
+    nb = int(block.numel())
+    dev = block.device
+    start = int(start)
+    if start < 0 or start > nb or (limit is not None and int(limit) < 0) or (capacity is not None and int(capacity) < 0):
+        raise SbeError("term_poll: start must lie in [0, block.numel()], limit and capacity must not be negative")
+    if nb % 32 or start % 32:
+        raise SbeError("term_poll: block.numel() and start must be multiples of 32")
+    if nb > TERM_MAX_BLOCK:
+        raise SbeError("term_poll: a block holds at most 2^30 bytes")
+    carry = _dev(carry, torch.uint8, "carry")
+    nc = 0 if carry is None else int(carry.numel())
+    bound = nc + nb - start
+    if bound > 1 << 31:
+        raise SbeError("term_poll: carry and block[start:] together exceed 2^31 bytes")
+    if capacity is None:
+        capacity = (nb - start) // 32 + 1
+        if limit is not None:
+            capacity = min(capacity, int(limit))
+    capacity = int(capacity)
+    lim = (1 << 64) - 1 if limit is None else int(limit)
+    if out is None:
+        out = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
+    elif _dev(out, torch.uint8, "out").numel() < bound:
+        raise SbeError("term_poll: out holds fewer than carry.numel() + block.numel() - start bytes")
+    if nc:
+        c0, o0 = carry.data_ptr(), out.data_ptr()
+        if c0 < o0 + out.numel() and o0 < c0 + nc:
+            raise SbeError("term_poll: carry overlaps out (alternate two out buffers)")
+    if msg_off is None:
+        msg_off = torch.empty(capacity + 1, dtype=torch.int64, device=dev)
+    elif _dev(msg_off, torch.int64, "msg_off").numel() < capacity + 1:
+        raise SbeError("term_poll: msg_off holds fewer than capacity + 1 entries")
+    counts = torch.empty(6, dtype=torch.int64, device=dev)
+    need = int(lib().sbe_term_poll_workspace_size(nb, capacity))
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    elif _dev(workspace, torch.uint8, "workspace").numel() < need:
+        raise SbeError(f"term_poll: workspace holds fewer than {need} bytes")
+    o = _TermPollOut(msg_off.data_ptr(), counts.data_ptr())
+    rc = lib().sbe_term_poll(_ptr(block) if nb else None, nb, start, lim, capacity, _ptr(carry) if nc else None, nc,
+                             _ptr(out), int(out.numel()), ctypes.byref(o), _ptr(workspace), workspace.numel(),
+                             _stream(stream))
+    _check(rc, "sbe_term_poll")
+    return TermMessages(out, msg_off, counts)
 
 
 # sbe_term_append: why the call stopped (counts[3])

@@ -89,6 +89,10 @@
  * sbe_term_scan()                 no reference source (third-party Aeron, TermReader::read): the walk
  *                                  over the 32-byte data-frame headers of a term-buffer block that
  *                                  hands fragments to onFragment src/cluster_client.cpp:39-82
+ * sbe_term_poll()                 that walk and onFragment src/cluster_client.cpp:39-82 in one call: a
+ *                                  raw block and the open accumulator in, whole messages out, the
+ *                                  fragment count handed on in device memory and every payload byte
+ *                                  copied once (sbe_term_poll_workspace_size)
  * sbe_term_append()               no reference source (third-party Aeron, ExclusivePublication::offer ->
  *                                  ExclusiveTermAppender): the data frames, fragmented at the MTU, and
  *                                  the end-of-term padding frame that the per-record offer behind
@@ -1064,6 +1068,48 @@ uint32_t sbe_term_scan_tile(void);
 int sbe_term_scan(const uint8_t* block, uint64_t block_bytes, uint64_t start, uint64_t fragment_limit,
                   uint64_t frag_capacity, uint8_t* out, const sbe_term_out* o, void* workspace,
                   size_t workspace_bytes, void* stream);
+
+/* sbe_term_scan and sbe_reassemble_fragments as one call: a raw block and the open accumulator of
+ * the calls before it in, whole messages out.  The fragment count stays in device memory (no host
+ * read between the walk and the reassembly) and each payload byte is copied once, from the block or
+ * the carry buffer straight into its message.
+ * Walk: exactly sbe_term_scan's, with limit = min(fragment_limit, frag_capacity), the same five stop
+ * reasons and the same rule for padding frames around the limit; counts[0..3] are what sbe_term_scan
+ * writes for the same block, start, limit and capacity.  The carry is no fragment of the walk: it
+ * does not count against the limit, is not in counts[0] or counts[2] and does not move `next`.
+ * Reassembly: exactly sbe_reassemble_fragments over the delivered fragments in delivery order; with
+ * carry_bytes > 0, one leading fragment with flags 0 that holds carry[0 .. carry_bytes) comes first.
+ * So a first fragment with BEGIN drops the carry; a first fragment that is a BEGIN|END single is
+ * delivered and the carry stays open; a first fragment with END delivers carry + fragment as one
+ * message; with no fragment delivered (limit 0, start == block_bytes, an immediate stop) m = 0 and
+ * the carry goes out unchanged.
+ * Outputs (device memory): the messages back to back from out[0], message j at out[msg_off[j] ..
+ * msg_off[j+1]) for j < m, msg_off[0] = 0; the open accumulator at out[msg_off[m] .. msg_off[m] +
+ * counts[5]); counts = {fragments, next, payload bytes, SBE_TERM_STOP_*, messages m, carry bytes}.
+ * Entries of msg_off past m and bytes of out past the carry are unspecified; nothing is written at
+ * or past out[carry_bytes + block_bytes - start].  m <= fragments, so frag_capacity + 1 offsets are
+ * enough.  To continue, pass the accumulator as the next call's carry: it may be a view of this
+ * call's out, and the next call then writes to a second buffer (carry and out must not overlap).
+ * SBE_EINVAL (before anything touches a device): everything sbe_term_scan refuses (block_bytes or
+ * start not a multiple of 32; start > block_bytes; block_bytes > 2^30; block not 16-B aligned; null
+ * block or workspace when block_bytes > start); null o / msg_off / counts / out; null carry with
+ * carry_bytes > 0; msg_off or counts not 8-B aligned; carry_bytes + block_bytes - start > 2^31;
+ * [carry, carry + carry_bytes) overlapping [out, out + out_capacity).  SBE_ENOSPC: out_capacity <
+ * carry_bytes + block_bytes - start; block_bytes > start and workspace_bytes <
+ * sbe_term_poll_workspace_size(block_bytes, frag_capacity).  A bad argument wins over a short buffer.
+ * Every launch is enqueued on `stream`; the call does not wait, copy to the host or allocate.
+ * block_bytes == start or limit == 0: one launch that writes counts and msg_off[0], and one that
+ * copies the carry when there is one; otherwise seven launches (three of the walk, three of the
+ * scan, the gather), and one more in front that enters the carry into the tables. */
+typedef struct sbe_term_poll_out {
+    uint64_t* msg_off;  /* [frag_capacity + 1]; message j = out[msg_off[j] .. msg_off[j+1]) for j < m */
+    uint64_t* counts;   /* [6] fragments, next, payload bytes, SBE_TERM_STOP_*, messages m, carry bytes */
+} sbe_term_poll_out;
+size_t sbe_term_poll_workspace_size(uint64_t block_bytes, uint64_t frag_capacity);
+int sbe_term_poll(const uint8_t* block, uint64_t block_bytes, uint64_t start, uint64_t fragment_limit,
+                  uint64_t frag_capacity, const uint8_t* carry, uint64_t carry_bytes,
+                  uint8_t* out, uint64_t out_capacity, const sbe_term_poll_out* o,
+                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* The publish side, the mirror of sbe_term_scan: a batch of encoded records (`in`, rec_off[n + 1], as
  * sbe_encode_session_batch, sbe_publish_orders_batch and sbe_emit_commit_offsets leave them) appended

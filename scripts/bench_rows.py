@@ -30,6 +30,8 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
                          frames of at most 1376 bytes) framed on the device (sbe_term_scan): the scan alone,
                          tables only, scan + reassembly, a device copy of the payload as the ceiling, and the
                          host mirror's one-thread term_walk with its payload memcpy
+  term_poll              the same block polled into whole messages by one call (sbe_term_poll), and the chain
+                         it replaces (sbe_term_scan with payload copy + sbe_reassemble_fragments), twice
   term_append            the records of that block (built first, encoded in device memory) appended to a 16 MiB
                          term-buffer block with Aeron's framing at MTU 1408 on the device (sbe_term_append),
                          a device copy of the same payload bytes as the ceiling, and the host mirror's
@@ -642,17 +644,9 @@ def row_order_select(steps, warmup):
         torch.cuda.empty_cache()
 
 
-def row_term_scan(steps, warmup):
-    """sbe_term_scan over a raw 16 MiB term-buffer block: config-3 records, session-framed, one
-    BEGIN|END frame each, with every 64th message a 6 KB TopicMessage in BEGIN / middle / END frames of
-    at most 1376 payload bytes.  Timed in the same run: the scan alone (tables and payload copy), the
-    scan with tables only, scan + sbe_reassemble_fragments, a device copy of the payload bytes (the
-    ceiling), and on the host the mirror's one-thread term_walk alone and with its payload memcpy
-    (tests/term/term_baseline)."""
-    import subprocess
-    import tempfile
+def _term_block(total):
+    """The block of the term_scan and term_poll rows, and its messages."""
     import termscan_lib as S
-    total = 16 << 20
     data, off = T.mixed_records(60_000)
     b = S.Block()
     long_payload = bytes(32 + j % 90 for j in range(6000))
@@ -668,7 +662,21 @@ def row_term_scan(steps, warmup):
             b.frame(rec[k: k + 1376], (S.BEGIN if k == 0 else 0) | (S.ENDF if k + 1376 >= len(rec) else 0))
         nmsg += 1
     b.pad_to(total)
-    blk = b.bytes()
+    return b.bytes(), nmsg
+
+
+def row_term_scan(steps, warmup):
+    """sbe_term_scan over a raw 16 MiB term-buffer block: config-3 records, session-framed, one
+    BEGIN|END frame each, with every 64th message a 6 KB TopicMessage in BEGIN / middle / END frames of
+    at most 1376 payload bytes.  Timed in the same run: the scan alone (tables and payload copy), the
+    scan with tables only, scan + sbe_reassemble_fragments, a device copy of the payload bytes (the
+    ceiling), and on the host the mirror's one-thread term_walk alone and with its payload memcpy
+    (tests/term/term_baseline)."""
+    import subprocess
+    import tempfile
+    import termscan_lib as S
+    total = 16 << 20
+    blk, nmsg = _term_block(total)
     w = S.walk(blk)
     n, pbytes = w["fragments"], w["frag_off"][-1]
     d0 = torch.from_numpy(np.frombuffer(blk, np.uint8).copy()).cuda()
@@ -721,6 +729,55 @@ def row_term_scan(steps, warmup):
     # the block's header sectors read twice (chain, emit), payload read and written, 12 B per slot
     # written and 12 B per tile entry read, the tables written
     line("term_scan", n, ms_scan * 1e-3, {"sbe_term_scan (3 launches)": (ms_scan, 2 * total + 2 * pbytes + 12 * (total // 32) + 13 * n)})
+
+
+def row_term_poll(steps, warmup):
+    """sbe_term_poll over the term_scan row's block (16 MiB, whole messages out in one call, no host
+    read), and in the same run the path it replaces for a device-resident caller: sbe_term_scan with
+    its payload copy, then sbe_reassemble_fragments with n known (the term_scan row's
+    scan_reassemble_ms), measured twice, so the spread between two measurements of one thing is on
+    record.  Device events over whole calls, rotated sets; the first call's counts, msg_off and every
+    message byte are checked against the restatements before timing."""
+    import termscan_lib as S
+    total = 16 << 20
+    blk, nmsg = _term_block(total)
+    w = S.walk(blk)
+    n, pbytes = w["fragments"], w["frag_off"][-1]
+    msgs, carry = T.oracle_reassemble(np.frombuffer(w["payload"], np.uint8), np.array(w["frag_off"], np.uint64),
+                                      np.array(w["flags"], np.uint8))
+    assert len(msgs) == nmsg and carry == b""
+    d0 = torch.from_numpy(np.frombuffer(blk, np.uint8).copy()).cuda()
+    ws = torch.empty(int(sbecodec.lib().sbe_term_scan_workspace_size(total)), dtype=torch.uint8, device="cuda")
+    rws = torch.empty(int(sbecodec.lib().sbe_reassemble_workspace_size(n)), dtype=torch.uint8, device="cuda")
+    pws = torch.empty(int(sbecodec.lib().sbe_term_poll_workspace_size(total, n + 1)), dtype=torch.uint8, device="cuda")
+    R = Rot(lambda k: (d0.clone(), torch.empty(total, dtype=torch.uint8, device="cuda"),
+                       torch.empty(total, dtype=torch.uint8, device="cuda"), torch.empty(n + 2, dtype=torch.int64, device="cuda")))
+    first = sbecodec.term_poll(d0, capacity=n + 1, workspace=pws)
+    torch.cuda.synchronize()
+    c = [int(x) for x in first.counts.cpu().numpy()]
+    assert c == [n, total, pbytes, S.END, nmsg, 0], c
+    mo = first.msg_off[: nmsg + 1].cpu().numpy()
+    assert mo.tolist() == np.concatenate([[0], np.cumsum([len(x) for x in msgs])]).tolist()
+    assert first.out[: int(mo[-1])].cpu().numpy().tobytes() == b"".join(msgs)
+
+    def poll():
+        d, out, _, mo = R.next()
+        sbecodec.term_poll(d, capacity=n + 1, out=out, msg_off=mo, workspace=pws)
+
+    def chain():  # n: the fragment count a caller reads from counts[0] (here known from the first call)
+        d, out, out2, mo = R.next()
+        s = sbecodec.term_scan(d, out=out, capacity=n + 1, workspace=ws)
+        sbecodec.reassemble(s.out, s.frag_off[: n + 1], s.flags[:n], out=out2, msg_off=mo, workspace=rws)
+
+    ms_chain, ms_poll, ms_chain2 = (_event_ms(f, steps, warmup) for f in (chain, poll, chain))
+    print(json.dumps({"row": "term_poll_detail", "block_bytes": total, "fragments": n, "messages": nmsg,
+                      "payload_bytes": pbytes, "term_poll_ms": ms_poll, "scan_reassemble_ms": ms_chain,
+                      "scan_reassemble_again_ms": ms_chain2, "spread_ms": abs(ms_chain - ms_chain2),
+                      "launches": "term_tile_chain, term_walk_tiles, term_emit, tp_frag_reduce, tp_frag_scan_blocks, "
+                                  "tp_frag_scan_msgs, term_poll_gather"}), flush=True)
+    # the block's header sectors read twice (chain, emit), payload read and written once, 12 B per
+    # slot written and 12 B per tile entry read, the fragment tables written and read by the scans
+    line("term_poll", n, ms_poll * 1e-3, {"sbe_term_poll (7 launches)": (ms_poll, 2 * total + 2 * pbytes + 12 * (total // 32) + 3 * 13 * n)})
 
 
 def row_term_append(steps, warmup):
@@ -1227,7 +1284,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,order_select,term_scan,term_append,commit_emit,commit_fallback,ack_correlate,delivery_track,delivery_report")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,order_select,term_scan,term_poll,term_append,commit_emit,commit_fallback,ack_correlate,delivery_track,delivery_report")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -1262,6 +1319,8 @@ def main():
             row_order_select(args.steps, args.warmup)
         elif r == "term_scan":
             row_term_scan(args.steps, args.warmup)
+        elif r == "term_poll":
+            row_term_poll(args.steps, args.warmup)
         elif r == "term_append":
             row_term_append(args.steps, args.warmup)
         elif r == "commit_emit":
