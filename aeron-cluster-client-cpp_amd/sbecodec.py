@@ -1576,12 +1576,14 @@ def term_scan_tile() -> int:
 
 
 def term_scan(block, start=0, limit=None, stream=None, capacity=None, out=None, want_out=True, want_src=True,
-              workspace=None) -> TermFragments:
+              workspace=None, frag_off=None, flags=None, frag_src=None, counts=None) -> TermFragments:
     """The fragments a poll of one image finds in a raw term-buffer block (whole frames with their
     32-byte Aeron data-frame headers), from offset `start`, at most `limit`: out / frag_off / flags
     and counts[0] are what reassemble takes.  block.numel() and start are multiples of 32.  capacity:
     entries of the tables (default: every slot of the block could be a fragment, or `limit`); out: a
-    tensor of block.numel() - start bytes to write the payloads to (want_out=False: tables only)."""
+    tensor of block.numel() - start bytes to write the payloads to (want_out=False: tables only).
+    frag_off (int64, capacity + 1), flags (uint8, capacity), frag_src (int32, capacity) and counts
+    (int64, 4): the caller's tables (default: allocated here)."""
     block = _dev(block, torch.uint8, "block")
     nb = int(block.numel())
     dev = block.device
@@ -1601,10 +1603,18 @@ def term_scan(block, start=0, limit=None, stream=None, capacity=None, out=None, 
         out = torch.empty(max(nb - start, 16), dtype=torch.uint8, device=dev)
     elif _dev(out, torch.uint8, "out").numel() < nb - start:
         raise SbeError("term_scan: out holds fewer than block.numel() - start bytes")
-    frag_off = torch.empty(capacity + 1, dtype=torch.int64, device=dev)
-    flags = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
-    frag_src = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev) if want_src else None
-    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    frag_off = torch.empty(capacity + 1, dtype=torch.int64, device=dev) if frag_off is None else \
+        _dev(frag_off, torch.int64, "frag_off")
+    flags = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev) if flags is None else _dev(flags, torch.uint8, "flags")
+    if not want_src:
+        frag_src = None
+    elif frag_src is None:
+        frag_src = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
+    frag_src = _dev(frag_src, torch.int32, "frag_src")
+    counts = torch.empty(4, dtype=torch.int64, device=dev) if counts is None else _dev(counts, torch.int64, "counts")
+    if frag_off.numel() < capacity + 1 or flags.numel() < capacity or counts.numel() < 4 or \
+            (frag_src is not None and frag_src.numel() < capacity):
+        raise SbeError("term_scan: frag_off / flags / frag_src / counts hold fewer than capacity (+ 1) / 4 elements")
     need = int(lib().sbe_term_scan_workspace_size(nb))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
@@ -1625,14 +1635,15 @@ class TermMessages:
 
 
 def term_poll(block, start=0, limit=None, carry=None, capacity=None, out=None, msg_off=None, workspace=None,
-              stream=None) -> TermMessages:
+              stream=None, counts=None) -> TermMessages:
     """term_scan and reassemble in one call: the whole messages a poll of one image finds in a raw
     term-buffer block from offset `start`, at most `limit` fragments.  carry: the open accumulator of
     the poll before (uint8 device tensor, e.g. a view out[msg_off[m]:msg_off[m] + counts[5]] of that
     call's result; it must not overlap this call's out, so two out buffers alternate).  The carry
     after this call is out[msg_off[m]:msg_off[m] + counts[5]] with m = counts[4].  capacity and limit
     default as in term_scan; out holds carry.numel() + block.numel() - start bytes, msg_off
-    capacity + 1 entries.  Nothing is read back: the counts stay on the device."""
+    capacity + 1 entries, counts (default: allocated here) 6.  Nothing is read back: the counts stay
+    on the device."""
     block = _dev(block, torch.uint8, "block")
     nb = int(block.numel())
     dev = block.device
@@ -1666,7 +1677,10 @@ def term_poll(block, start=0, limit=None, carry=None, capacity=None, out=None, m
         msg_off = torch.empty(capacity + 1, dtype=torch.int64, device=dev)
     elif _dev(msg_off, torch.int64, "msg_off").numel() < capacity + 1:
         raise SbeError("term_poll: msg_off holds fewer than capacity + 1 entries")
-    counts = torch.empty(6, dtype=torch.int64, device=dev)
+    if counts is None:
+        counts = torch.empty(6, dtype=torch.int64, device=dev)
+    elif _dev(counts, torch.int64, "counts").numel() < 6:
+        raise SbeError("term_poll: counts holds fewer than 6 elements")
     need = int(lib().sbe_term_poll_workspace_size(nb, capacity))
     if workspace is None:
         workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
@@ -1716,7 +1730,7 @@ def term_frames_length(length, mtu=1408) -> int:
 
 
 def term_append(block, data, rec_off, start=0, limit=None, mtu=1408, max_message_length=None, header=TermHeader(),
-                stream=None, workspace=None, rec_tail=None, want_tail=True) -> TermAppended:
+                stream=None, workspace=None, rec_tail=None, want_tail=True, counts=None) -> TermAppended:
     """Appends records data[rec_off[i]:rec_off[i+1]] (an encoder's out / out_off) to the raw
     term-buffer block from offset `start` with Aeron's framing: one BEGIN|END data frame a record, or
     BEGIN / middle / END frames of mtu - 32 payload bytes, and a padding-frame header where the block
@@ -1724,8 +1738,8 @@ def term_append(block, data, rec_off, start=0, limit=None, mtu=1408, max_message
     counts[0] in the next term).  block.numel() and start are multiples of 32.  limit: a record is
     refused once the tail is at or behind it (default: none); max_message_length: default Aeron's
     rule for a term of block.numel() bytes, min(numel / 8, 16 MiB); rec_tail: an int64 tensor of
-    rec_off.numel() - 1 elements to write the tails to (want_tail=False: none).  data and block
-    must not overlap."""
+    rec_off.numel() - 1 elements to write the tails to (want_tail=False: none); counts: an int64
+    tensor of 4 elements (default: allocated here).  data and block must not overlap."""
     block = _dev(block, torch.uint8, "block")
     data = _dev(data, torch.uint8, "data")
     rec_off = _dev(rec_off, torch.int64, "rec_off")
@@ -1742,7 +1756,10 @@ def term_append(block, data, rec_off, start=0, limit=None, mtu=1408, max_message
         rec_tail = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
     elif _dev(rec_tail, torch.int64, "rec_tail").numel() < n:
         raise SbeError("term_append: rec_tail holds fewer than rec_off.numel() - 1 elements")
-    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    if counts is None:
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+    elif _dev(counts, torch.int64, "counts").numel() < 4:
+        raise SbeError("term_append: counts holds fewer than 4 elements")
     need = int(lib().sbe_term_append_workspace_size(n))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)

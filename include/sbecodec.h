@@ -9,7 +9,8 @@
  * every call is an asynchronous launch on `stream` and returns after argument validation.
  * Every launch and memset of a call goes to `stream` and to no other stream.  A call writes the
  * output elements its comment names and nothing else: no byte before or after an output array,
- * and no byte outside the workspace size it asks for.
+ * and no byte outside the workspace size it asks for.  A workspace needs no particular contents:
+ * a call writes every workspace word before it reads it (a workspace serves one stream at a time).
  * Offset arrays (rec_off, frag_off) need not start at 0: they index `in`, so records a..b of a
  * larger batch are processed by passing rec_off + a with n = b - a (and in_bytes = rec_off[b] -
  * rec_off[a]); the per-record outputs of that call start at element 0 of the arrays it is given

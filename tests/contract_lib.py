@@ -130,6 +130,22 @@ class PoisonRun:
         bad = np.nonzero(b != self.poison)[0]
         assert bad.size == 0, f"{name}: {bad.size} bytes written where nothing may be, first at byte {lo + bad[:6]}"
 
+    def expect_head(self, name, exp):
+        """Elements [0, len(exp)) of buffer `name` equal exp, and every byte behind them, to the end
+        of the array, was not written: a table whose length the device decides."""
+        exp = np.asarray(exp).reshape(-1)
+        self.expect(name, exp)
+        self.expect_poison(name, exp.size * self.bufs[name].t.element_size())
+
+    def expect_rows(self, name, exp, lo, per=1):
+        """Rows [lo, lo + len(exp) / per) of buffer `name` (`per` elements a row) equal exp, and the
+        rows in front of them and behind them were not written: a slice filled in place."""
+        exp = np.asarray(exp).reshape(-1)
+        item = self.bufs[name].t.element_size()
+        self.expect(name, exp, lo=lo * per)
+        self.expect_poison(name, 0, lo * per * item)
+        self.expect_poison(name, (lo * per + exp.size) * item)
+
     def check_guards(self):
         for g in self.bufs.values():
             g.check_guards()
@@ -142,6 +158,18 @@ def twice(fn, device="cuda"):
         run = PoisonRun(poison, device)
         fn(run)
         run.check_guards()
+
+
+def workspace_history(ws, big, small, fills=(0xFF, 0x00)):
+    """The runs of a workspace-contents test on one workspace tensor `ws`: big(ws), then small(ws)
+    on what the big call left, then for every fill byte small and big again, each on a workspace
+    filled with that byte right before it.  big / small make the call and compare its outputs."""
+    big(ws)
+    small(ws)  # stale from the larger call
+    for fill in fills:
+        for call in (small, big):
+            ws.fill_(fill)
+            call(ws)
 
 
 def frag_scan_block():

@@ -80,6 +80,45 @@ def test_expect_poison_and_mismatch_message():
     assert "status: 2 of 3 elements differ" in msg and "1 of them still hold the poison 0x5A" in msg
 
 
+def test_expect_head_reports_a_write_behind_the_table():
+    """A table of device-decided length: entries 0..k hold the values, the rest the poison."""
+    def call(run, stray):
+        t = run.buf("frag_off", 6, torch.int64)
+        t[:3] = torch.tensor([0, 5, 9])
+        if stray is not None:
+            t[stray] = 9
+        run.expect_head("frag_off", [0, 5, 9])
+
+    C.twice(lambda run: call(run, None), device="cpu")
+    with pytest.raises(AssertionError, match="frag_off: 8 bytes written where nothing may be, first at byte \\[40"):
+        C.twice(lambda run: call(run, 5), device="cpu")
+    with pytest.raises(AssertionError, match="frag_off: 1 of 3 elements differ"):
+        C.twice(lambda run: call(run, 1), device="cpu")
+
+
+def test_expect_rows_reports_writes_outside_the_slice():
+    def call(run, stray):
+        t = run.buf("view_off", 5 * 6, torch.int32)
+        t[5 * 2: 5 * 4] = torch.arange(10, dtype=torch.int32)
+        if stray is not None:
+            t[stray] = 1
+        run.expect_rows("view_off", np.arange(10), 2, per=5)
+
+    C.twice(lambda run: call(run, None), device="cpu")
+    for stray, first in ((9, 36), (20, 80), (29, 116)):  # the row in front, the row behind, the last element
+        with pytest.raises(AssertionError, match="view_off: 4 bytes written where nothing may be, first at byte \\[%d" % first):
+            C.twice(lambda run: call(run, stray), device="cpu")
+
+
+def test_workspace_history_order_and_fills():
+    ws = torch.full((8,), 0x5A, dtype=torch.uint8)
+    seen = []
+    C.workspace_history(ws, lambda w: (seen.append(("big", int(w[0]))), w.fill_(1)),
+                        lambda w: (seen.append(("small", int(w[0]))), w.fill_(2)), fills=(0xFF, 0x00, 0x80))
+    assert seen == [("big", 0x5A), ("small", 1), ("small", 0xFF), ("big", 0xFF), ("small", 0), ("big", 0),
+                    ("small", 0x80), ("big", 0x80)]
+
+
 def test_minimal_alignment_and_placed_inputs():
     assert C.min_shift(torch.int64) == 8 and C.min_shift(torch.uint8) == 1 and C.min_shift(torch.uint8, 16) == 16
     off = np.arange(7, dtype=np.uint64) * 3
