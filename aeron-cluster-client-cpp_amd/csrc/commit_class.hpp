@@ -473,7 +473,7 @@ __device__ __forceinline__ uint64_t cm_wave_max64(uint64_t v) {
 }
 
 // One wave per 64-record tile, one lane per record.
-__global__ __launch_bounds__(kWave) void sbe_commit_kernel(CmArgs a) {
+__device__ __forceinline__ void cm_tile(const CmArgs& a) {
     __shared__ __attribute__((aligned(16))) uint8_t win[kCmWin + 16];
     __shared__ uint32_t hits[kCmWin / 16];
     __shared__ uint32_t toff[SBE_COMMIT_MAX_TOPICS + 1];
@@ -592,5 +592,13 @@ __global__ __launch_bounds__(kWave) void sbe_commit_kernel(CmArgs a) {
         }
         todo &= ~m;
     }
+}
+__global__ __launch_bounds__(kWave) void sbe_commit_kernel(CmArgs a) { cm_tile(a); }
+// sbe_classify_commits_counted: a.n is the capacity the grid was laid out by; a tile past the count
+// exits behind the load of the count.
+__global__ __launch_bounds__(kWave) void sbe_commit_counted_kernel(CmArgs a, const uint64_t* n_dev) {
+    a.n = counted_n(n_dev, a.n);
+    if ((uint64_t)blockIdx.x * kTile >= a.n) return;
+    cm_tile(a);
 }
 #endif

@@ -222,7 +222,7 @@ __device__ __forceinline__ Place write_head(const CeOut& a, uint64_t i0, uint32_
 }
 
 // Sizing launch: status and frame bytes per record (size_tail).
-__global__ __launch_bounds__(kBlock) void commit_emit_measure(CeArgs a) {
+__device__ __forceinline__ void emit_measure_block(const CeArgs& a) {
     __shared__ uint64_t wtot[kBlock / kWave];
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     uint32_t len = 0, st = SBE_CE_NONE;
@@ -232,6 +232,22 @@ __global__ __launch_bounds__(kBlock) void commit_emit_measure(CeArgs a) {
         a.o.sz[i] = len;
     }
     size_tail(a.o, st, len, wtot);
+}
+__global__ __launch_bounds__(kBlock) void commit_emit_measure(CeArgs a) { emit_measure_block(a); }
+
+// The *_counted launches: o.n is the capacity the grids, the workspace and the block-sum arrays were
+// laid out by.  A sizing block past the count leaves zero sums (size_tail on records without
+// frames), so one scan over the arrays of the capacity gives the prefixes and totals of the count.
+// A writing tile past the count exits, but for tile 0, which stores the totals (and out_off[0] of
+// an empty batch).
+__device__ __forceinline__ bool counted_write_tile(CeOut& o, const uint64_t* n_dev) {
+    o.n = counted_n(n_dev, o.n);
+    if (o.n == 0 && blockIdx.x == 0 && threadIdx.x == 0) o.out_off[0] = 0;
+    return blockIdx.x == 0 || (uint64_t)blockIdx.x * kWWave < o.n;
+}
+__global__ __launch_bounds__(kBlock) void commit_emit_measure_counted(CeArgs a, const uint64_t* n_dev) {
+    a.o.n = counted_n(n_dev, a.o.n);
+    emit_measure_block(a);
 }
 // Writing launch: one wave per tile of 64 records.  A typical framed record is ~100 bytes (32 + 24
 // + a 36-byte id + a short identifier), so a tile's frames fit the window in one pass; a frame
@@ -243,7 +259,7 @@ __global__ __launch_bounds__(kBlock) void commit_emit_measure(CeArgs a) {
 constexpr uint32_t kCeWin = SBE_CE_WIN;
 static_assert(kCeWin >= 4096 && kCeWin % 16 == 0 && kBlock % kWWave == 0, "a writing tile lies inside one sizing block");
 
-__global__ __launch_bounds__(kWWave) void commit_emit_write(CeArgs a) {
+__device__ __forceinline__ void emit_write_tile(const CeArgs& a) {
     __shared__ __attribute__((aligned(16))) uint8_t win[kCeWin];
     const uint32_t lane = threadIdx.x;
     const uint64_t i0 = (uint64_t)blockIdx.x * kWWave, i = i0 + lane;
@@ -256,6 +272,10 @@ __global__ __launch_bounds__(kWWave) void commit_emit_write(CeArgs a) {
     write_staged<kCeWin>(a.o.out, (lw8*)win, lane, todo, o, e, [&](auto& s) {
         ce_frame(s, a.c, f, [](auto& t, const uint8_t* p, uint32_t m) { t = pub::raw(t, (gu8*)p, m); });
     });
+}
+__global__ __launch_bounds__(kWWave) void commit_emit_write(CeArgs a) { emit_write_tile(a); }
+__global__ __launch_bounds__(kWWave) void commit_emit_write_counted(CeArgs a, const uint64_t* n_dev) {
+    if (counted_write_tile(a.o, n_dev)) emit_write_tile(a);
 }
 
 }  // namespace ce

@@ -246,7 +246,7 @@ __device__ __forceinline__ uint64_t text_bytes(const CfRec& r) {
 }
 
 // Sizing launch: as commit_emit_measure, the text of a JSON record measured on the way.
-__global__ __launch_bounds__(kBlock) void commit_fallback_measure(CfArgs a) {
+__device__ __forceinline__ void fallback_measure_block(const CfArgs& a) {
     __shared__ uint64_t wtot[kBlock / kWave];
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     uint32_t len = 0, st = SBE_CE_NONE;
@@ -256,6 +256,12 @@ __global__ __launch_bounds__(kBlock) void commit_fallback_measure(CfArgs a) {
         a.o.sz[i] = len;
     }
     ce::size_tail(a.o, st, len, wtot);
+}
+__global__ __launch_bounds__(kBlock) void commit_fallback_measure(CfArgs a) { fallback_measure_block(a); }
+// the *_counted launches: as commit_emit_measure_counted / commit_emit_write_counted
+__global__ __launch_bounds__(kBlock) void commit_fallback_measure_counted(CfArgs a, const uint64_t* n_dev) {
+    a.o.n = counted_n(n_dev, a.o.n);
+    fallback_measure_block(a);
 }
 
 // Writing launch: one wave per tile of 64 records, as commit_emit_write.  A JSON frame with short
@@ -273,7 +279,7 @@ static_assert(kCfWin >= 4096 && kCfWin % 16 == 0 && kCfWin <= 65536, "the window
 #define SBE_CF_MINW 2
 #endif
 
-__global__ __launch_bounds__(kWWave, SBE_CF_MINW) void commit_fallback_write(CfArgs a) {
+__device__ __forceinline__ void fallback_write_tile(const CfArgs& a) {
     __shared__ __attribute__((aligned(16))) uint8_t win[kCfWin];
     const uint32_t lane = threadIdx.x;
     const uint64_t i0 = (uint64_t)blockIdx.x * kWWave, i = i0 + lane;
@@ -305,6 +311,10 @@ __global__ __launch_bounds__(kWWave, SBE_CF_MINW) void commit_fallback_write(CfA
         else
             ce_frame(s, a.f.c, f, copy);
     });
+}
+__global__ __launch_bounds__(kWWave, SBE_CF_MINW) void commit_fallback_write(CfArgs a) { fallback_write_tile(a); }
+__global__ __launch_bounds__(kWWave, SBE_CF_MINW) void commit_fallback_write_counted(CfArgs a, const uint64_t* n_dev) {
+    if (ce::counted_write_tile(a.o, n_dev)) fallback_write_tile(a);
 }
 
 }  // namespace cf

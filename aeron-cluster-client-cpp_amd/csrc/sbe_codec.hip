@@ -3157,6 +3157,22 @@ __global__ __launch_bounds__(kWave, kWin == kWinWide && kWinWide > 16384 ? 2 : (
     dec_tile<kMode, kWin>(a, blockIdx.x, win);
 }
 
+// The record count of a *_counted call: min(*n_dev, capacity), one scalar load, the same in every lane.
+__device__ __forceinline__ uint64_t counted_n(const uint64_t* n_dev, uint64_t capacity) {
+    const uint64_t c = uniform64(*n_dev);
+    return c < capacity ? c : capacity;
+}
+
+// sbe_decode_batch_counted: the grid is laid out by the capacity (a.n on entry), a tile past the
+// count exits behind the load of the count, the others run dec_tile as sbe_decode_kernel does.
+template <uint32_t kMode, uint32_t kWin>
+__global__ __launch_bounds__(kWave, kWin == kWinWide && kWinWide > 16384 ? 2 : ((kWin == kWinWide || kWin == kWinLarge) ? SBE_DEC_MINW_WIDE : SBE_DEC_MINW)) void sbe_decode_counted_kernel(DecArgs a, const uint64_t* n_dev) {
+    __shared__ uint32_t win[kWin / 4];
+    a.n = counted_n(n_dev, a.n);
+    if ((uint64_t)blockIdx.x * kTile >= a.n) return;
+    dec_tile<kMode, kWin>(a, blockIdx.x, win);
+}
+
 thread_local char g_last_error[256] = "";
 
 int record_hip(hipError_t e) {
@@ -4610,6 +4626,78 @@ int commit_launches(void (*measure)(Args), void (*write)(Args), const Args& a, c
     hipLaunchKernelGGL(write, dim3((uint32_t)((o.n + oj::kWWave - 1) / oj::kWWave)), dim3(oj::kWWave), 0, s, a);
     return record_hip(hipGetLastError());
 }
+// The same three launches for sbe_emit_commit_offsets_counted: o.n is the capacity, which lays out the
+// grids and the block sums; the kernels take the count from *n_dev.
+template <class Args>
+int commit_launches_counted(void (*measure)(Args, const uint64_t*), void (*write)(Args, const uint64_t*), const Args& a,
+                            const ce::CeOut& o, const uint64_t* n_dev, hipStream_t s) {
+    const uint64_t nblk = (o.n + oj::kBlock - 1) / oj::kBlock;
+    hipLaunchKernelGGL(measure, dim3((uint32_t)nblk), dim3(oj::kBlock), 0, s, a, n_dev);
+    hipLaunchKernelGGL(oj::order_json_scan_blocks, dim3(1), dim3(oj::kScanThreads), 0, s, o.blk_bytes, 2 * (nblk + 1));
+    hipLaunchKernelGGL(write, dim3((uint32_t)((o.n + oj::kWWave - 1) / oj::kWWave)), dim3(oj::kWWave), 0, s, a, n_dev);
+    return record_hip(hipGetLastError());
+}
+
+// sbe_emit_commit_offsets_ex (counted false: n records, n_dev unused) and sbe_emit_commit_offsets_counted
+// (counted true: n is the capacity).  `counted` is an argument of its own because n_dev cannot say it: a
+// counted call with a null n_dev is a bad argument, not an uncounted call.
+int emit_commit_offsets(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const uint64_t* n_dev, bool counted,
+                        const sbe_decoded* dec, const sbe_commit_out* plan, const uint32_t* topic_id,
+                        const uint8_t* ident_arena, const uint32_t* ident_off, uint32_t k, const uint8_t* mask,
+                        uint32_t flags, int session, int64_t leadership_term_id, int64_t cluster_session_id,
+                        uint8_t* out, uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
+                        size_t workspace_bytes, void* stream, const sbe_commit_fallback* fb) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (fb && (!fb->topic_arena || !fb->topic_off || !fb->default_ident || misaligned(fb->topic_off, 3) ||
+               fb->default_ident_len > SBE_COMMIT_TABLE_BYTES))
+        return SBE_EINVAL;
+    if (!res || !res->out_off || !res->totals || misaligned(res->out_off, 7) || misaligned(res->totals, 7) ||
+        misaligned(res->emit_idx, 7))
+        return SBE_EINVAL;
+    if (k == 0 || k > SBE_COMMIT_MAX_TOPICS || (flags & ~SBE_CE_LAST_ONLY) || ((flags & SBE_CE_LAST_ONLY) && mask) ||
+        (session != 0 && session != 1) || (!out && out_capacity) || n >= (1ull << 32))
+        return SBE_EINVAL;
+    if (n == 0) {
+        if (const int rc = record_hip(hipMemsetAsync(res->out_off, 0, 8, s))) return rc;
+        return record_hip(hipMemsetAsync(res->totals, 0, 24, s));
+    }
+    if (!in || !rec_off || !dec || !dec->status || !dec->flags || !dec->view_off || !dec->view_len || !plan ||
+        !plan->cm || !plan->topic_idx || ((flags & SBE_CE_LAST_ONLY) && !plan->last) || !topic_id || !ident_arena ||
+        !ident_off || !res->status || !workspace)
+        return SBE_EINVAL;
+    if (misaligned(rec_off, 7) || misaligned(dec->view_off, 3) || misaligned(dec->view_len, 3) ||
+        misaligned(dec->seq, 7) || misaligned(plan->topic_idx, 3) ||
+        ((flags & SBE_CE_LAST_ONLY) && misaligned(plan->last, 7)) || misaligned(topic_id, 3) ||
+        misaligned(ident_off, 3) || misaligned(workspace, 15))
+        return SBE_EINVAL;
+    if (fb && (!dec->ts || !plan->topic_kind || !plan->topic_off || !plan->topic_len || misaligned(dec->ts, 7) ||
+               misaligned(plan->topic_off, 3) || misaligned(plan->topic_len, 3)))
+        return SBE_EINVAL;
+    if (counted && (!n_dev || misaligned(n_dev, 7))) return SBE_EINVAL;
+    if (workspace_bytes < sbe_commit_emit_workspace_size(n)) return SBE_ENOSPC;
+    const uint64_t nblk = (n + oj::kBlock - 1) / oj::kBlock;
+    const CeIn c{in,          rec_off,   dec->status, dec->flags, dec->view_off, dec->view_len,
+                 dec->seq,    plan->cm,  plan->topic_idx, plan->last, topic_id,  ident_arena,
+                 ident_off,   k,         mask,        flags,      (uint32_t)session, leadership_term_id,
+                 cluster_session_id};
+    Carver ws(workspace);
+    uint32_t* sz = ws.take<uint32_t>(n);
+    uint64_t* blk = ws.take<uint64_t>(2 * (nblk + 1));  // bytes, counts behind them: one scan runs over both
+    const ce::CeOut o{n,  out, out_capacity, res->out_off, res->status, res->emit_idx, res->totals,
+                      sz, blk, blk + (nblk + 1)};
+    if (!fb) {
+        if (counted)
+            return commit_launches_counted(ce::commit_emit_measure_counted, ce::commit_emit_write_counted,
+                                           ce::CeArgs{c, o}, o, n_dev, s);
+        return commit_launches(ce::commit_emit_measure, ce::commit_emit_write, ce::CeArgs{c, o}, o, s);
+    }
+    const CfIn f{c,           dec->ts,       plan->topic_kind,  plan->topic_off,       plan->topic_len, fb->topic_arena,
+                 fb->topic_off, fb->default_ident, fb->default_ident_len, fb->now_ns, fb->uuid_ns};
+    if (counted)
+        return commit_launches_counted(cf::commit_fallback_measure_counted, cf::commit_fallback_write_counted,
+                                       cf::CfArgs{f, o}, o, n_dev, s);
+    return commit_launches(cf::commit_fallback_measure, cf::commit_fallback_write, cf::CfArgs{f, o}, o, s);
+}
 
 }  // namespace
 
@@ -4738,6 +4826,44 @@ int sbe_decode_batch_sized(const uint8_t* in, const uint64_t* rec_off, uint64_t 
 int sbe_decode_batch(const uint8_t* in, const uint64_t* rec_off, uint64_t n, uint32_t mode,
                      const sbe_decoded* out, void* stream) {
     return sbe_decode_batch_sized(in, rec_off, n, 0, mode, out, stream);
+}
+
+int sbe_decode_batch_counted(const uint8_t* in, const uint64_t* rec_off, const uint64_t* n_dev, uint64_t n_capacity,
+                             uint64_t avg_record_bytes, uint32_t mode, const sbe_decoded* out, void* stream) {
+    if (const int rc = dec_check(in, rec_off, n_capacity, mode, out)) return rc;
+    if (n_capacity == 0) return SBE_OK;
+    if (!n_dev || misaligned(n_dev, 7)) return SBE_EINVAL;
+    const uint64_t tiles = (n_capacity + kTile - 1) / kTile;
+    DecArgs a{in,           rec_off,       n_capacity,
+              out->status,  out->flags,    out->hdr,
+              out->ts,      out->view_off, out->view_len,
+              mode == SBE_DEC_PARSE_MESSAGE ? out->seq : nullptr};
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((uint32_t)tiles), block(kWave);
+    // the thresholds of sbe_decode_batch_sized, on the caller's average (0: unknown, the 16 KiB window)
+    const uint64_t avg = avg_record_bytes;
+    const int shape = avg > kLargeAvg ? 4 : avg > kWideAvg ? 1 : avg == 0 ? 0 : avg <= kSmallAvg ? 3 : avg <= kMidAvg ? 2 : 0;
+#define SBE_DEC_LAUNCH(M)                                                                                   \
+    do {                                                                                                    \
+        if (shape == 4)                                                                                     \
+            hipLaunchKernelGGL((sbe_decode_counted_kernel<M, kWinLarge>), grid, block, 0, s, a, n_dev);     \
+        else if (shape == 1)                                                                                \
+            hipLaunchKernelGGL((sbe_decode_counted_kernel<M, kWinWide>), grid, block, 0, s, a, n_dev);      \
+        else if (shape == 2)                                                                                \
+            hipLaunchKernelGGL((sbe_decode_counted_kernel<M, kWinMid>), grid, block, 0, s, a, n_dev);       \
+        else if (shape == 3)                                                                                \
+            hipLaunchKernelGGL((sbe_decode_counted_kernel<M, kWinSmall>), grid, block, 0, s, a, n_dev);     \
+        else                                                                                                \
+            hipLaunchKernelGGL((sbe_decode_counted_kernel<M, kWin>), grid, block, 0, s, a, n_dev);          \
+    } while (0)
+    if (mode == SBE_DEC_ON_EGRESS)
+        SBE_DEC_LAUNCH(SBE_DEC_ON_EGRESS);
+    else if (mode == SBE_DEC_LITE)
+        SBE_DEC_LAUNCH(SBE_DEC_LITE);
+    else
+        SBE_DEC_LAUNCH(SBE_DEC_PARSE_MESSAGE);
+#undef SBE_DEC_LAUNCH
+    return record_hip(hipGetLastError());
 }
 
 int sbe_server_create(sbe_server** srv, uint32_t idle_us) { return sbe_server_create_wide(srv, idle_us, 1); }
@@ -5069,6 +5195,33 @@ int sbe_classify_commits(const uint8_t* in, const uint64_t* rec_off, uint64_t n,
     return record_hip(hipGetLastError());
 }
 
+int sbe_classify_commits_counted(const uint8_t* in, const uint64_t* rec_off, const uint64_t* n_dev, uint64_t n_capacity,
+                                 const sbe_decoded* dec, const uint8_t* topic_arena, const uint32_t* topic_off,
+                                 uint32_t k, const sbe_commit_out* out, void*, size_t, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const uint64_t n = n_capacity;
+    if (!out || !out->last || !out->count || misaligned(out->last, 7) || misaligned(out->count, 7)) return SBE_EINVAL;
+    if (k == 0 || k > SBE_COMMIT_MAX_TOPICS) return SBE_EINVAL;
+    if (n && (!in || !rec_off || !dec || !dec->status || !dec->flags || !dec->view_off || !dec->view_len ||
+              !topic_arena || !topic_off || !out->cm || !out->topic_src || !out->topic_kind || !out->topic_off ||
+              !out->topic_len || !out->topic_idx || !n_dev))
+        return SBE_EINVAL;
+    if (n && (misaligned(rec_off, 7) || misaligned(dec->view_off, 3) || misaligned(dec->view_len, 3) ||
+              misaligned(topic_off, 3) || misaligned(out->topic_off, 3) || misaligned(out->topic_len, 3) ||
+              misaligned(out->topic_idx, 3) || misaligned(n_dev, 7)))
+        return SBE_EINVAL;
+    const uint64_t tiles = (n + kTile - 1) / kTile;
+    if (tiles > 0x7fffffffull) return SBE_EINVAL;
+    hipLaunchKernelGGL(sbe_commit_init, dim3(1), dim3(kWave), 0, s, out->last, out->count, k);
+    if (n) {
+        CmArgs a{in,           rec_off,        n,          dec->status,    dec->flags,     dec->view_off,
+                 dec->view_len, topic_arena,   topic_off,  k,              out->cm,        out->topic_src,
+                 out->topic_kind, out->topic_off, out->topic_len, out->topic_idx, out->last, out->count};
+        hipLaunchKernelGGL(sbe_commit_counted_kernel, dim3((uint32_t)tiles), dim3(kWave), 0, s, a, n_dev);
+    }
+    return record_hip(hipGetLastError());
+}
+
 size_t sbe_json_extract_workspace_size(uint64_t, uint32_t) { return 0; }
 
 int sbe_json_extract_batch(const uint8_t* in, const uint64_t* rec_off, uint64_t n, const sbe_decoded* dec,
@@ -5138,47 +5291,21 @@ int sbe_emit_commit_offsets_ex(const uint8_t* in, const uint64_t* rec_off, uint6
                                int session, int64_t leadership_term_id, int64_t cluster_session_id, uint8_t* out,
                                uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
                                size_t workspace_bytes, void* stream, const sbe_commit_fallback* fb) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (fb && (!fb->topic_arena || !fb->topic_off || !fb->default_ident || misaligned(fb->topic_off, 3) ||
-               fb->default_ident_len > SBE_COMMIT_TABLE_BYTES))
-        return SBE_EINVAL;
-    if (!res || !res->out_off || !res->totals || misaligned(res->out_off, 7) || misaligned(res->totals, 7) ||
-        misaligned(res->emit_idx, 7))
-        return SBE_EINVAL;
-    if (k == 0 || k > SBE_COMMIT_MAX_TOPICS || (flags & ~SBE_CE_LAST_ONLY) || ((flags & SBE_CE_LAST_ONLY) && mask) ||
-        (session != 0 && session != 1) || (!out && out_capacity) || n >= (1ull << 32))
-        return SBE_EINVAL;
-    if (n == 0) {
-        if (const int rc = record_hip(hipMemsetAsync(res->out_off, 0, 8, s))) return rc;
-        return record_hip(hipMemsetAsync(res->totals, 0, 24, s));
-    }
-    if (!in || !rec_off || !dec || !dec->status || !dec->flags || !dec->view_off || !dec->view_len || !plan ||
-        !plan->cm || !plan->topic_idx || ((flags & SBE_CE_LAST_ONLY) && !plan->last) || !topic_id || !ident_arena ||
-        !ident_off || !res->status || !workspace)
-        return SBE_EINVAL;
-    if (misaligned(rec_off, 7) || misaligned(dec->view_off, 3) || misaligned(dec->view_len, 3) ||
-        misaligned(dec->seq, 7) || misaligned(plan->topic_idx, 3) ||
-        ((flags & SBE_CE_LAST_ONLY) && misaligned(plan->last, 7)) || misaligned(topic_id, 3) ||
-        misaligned(ident_off, 3) || misaligned(workspace, 15))
-        return SBE_EINVAL;
-    if (fb && (!dec->ts || !plan->topic_kind || !plan->topic_off || !plan->topic_len || misaligned(dec->ts, 7) ||
-               misaligned(plan->topic_off, 3) || misaligned(plan->topic_len, 3)))
-        return SBE_EINVAL;
-    if (workspace_bytes < sbe_commit_emit_workspace_size(n)) return SBE_ENOSPC;
-    const uint64_t nblk = (n + oj::kBlock - 1) / oj::kBlock;
-    const CeIn c{in,          rec_off,   dec->status, dec->flags, dec->view_off, dec->view_len,
-                 dec->seq,    plan->cm,  plan->topic_idx, plan->last, topic_id,  ident_arena,
-                 ident_off,   k,         mask,        flags,      (uint32_t)session, leadership_term_id,
-                 cluster_session_id};
-    Carver ws(workspace);
-    uint32_t* sz = ws.take<uint32_t>(n);
-    uint64_t* blk = ws.take<uint64_t>(2 * (nblk + 1));  // bytes, counts behind them: one scan runs over both
-    const ce::CeOut o{n,  out, out_capacity, res->out_off, res->status, res->emit_idx, res->totals,
-                      sz, blk, blk + (nblk + 1)};
-    if (!fb) return commit_launches(ce::commit_emit_measure, ce::commit_emit_write, ce::CeArgs{c, o}, o, s);
-    const CfIn f{c,           dec->ts,       plan->topic_kind,  plan->topic_off,       plan->topic_len, fb->topic_arena,
-                 fb->topic_off, fb->default_ident, fb->default_ident_len, fb->now_ns, fb->uuid_ns};
-    return commit_launches(cf::commit_fallback_measure, cf::commit_fallback_write, cf::CfArgs{f, o}, o, s);
+    return emit_commit_offsets(in, rec_off, n, nullptr, false, dec, plan, topic_id, ident_arena, ident_off, k, mask, flags,
+                               session, leadership_term_id, cluster_session_id, out, out_capacity, res, workspace,
+                               workspace_bytes, stream, fb);
+}
+
+int sbe_emit_commit_offsets_counted(const uint8_t* in, const uint64_t* rec_off, const uint64_t* n_dev,
+                                    uint64_t n_capacity, const sbe_decoded* dec, const sbe_commit_out* plan,
+                                    const uint32_t* topic_id, const uint8_t* ident_arena, const uint32_t* ident_off,
+                                    uint32_t k, const uint8_t* mask, uint32_t flags, int session,
+                                    int64_t leadership_term_id, int64_t cluster_session_id, uint8_t* out,
+                                    uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
+                                    size_t workspace_bytes, void* stream, const sbe_commit_fallback* fb) {
+    return emit_commit_offsets(in, rec_off, n_capacity, n_dev, true, dec, plan, topic_id, ident_arena, ident_off, k, mask,
+                               flags, session, leadership_term_id, cluster_session_id, out, out_capacity, res,
+                               workspace, workspace_bytes, stream, fb);
 }
 
 size_t sbe_inflight_table_size(uint64_t capacity) {
@@ -5671,6 +5798,44 @@ int sbe_term_append(const uint8_t* in, uint64_t in_bytes, const uint64_t* rec_of
     hipLaunchKernelGGL(ta_tails, dim3((uint32_t)nb), dim3(kTaBlk), 0, s, a);
     const uint32_t tile0 = (uint32_t)(start / kTaTile), nt = (uint32_t)((block_bytes + kTaTile - 1) / kTaTile) - tile0;
     if (block_bytes > start) hipLaunchKernelGGL(ta_write, dim3(nt), dim3(kTaThreads), 0, s, a, tile0);
+    return record_hip(hipGetLastError());
+}
+
+int sbe_term_append_counted(const uint8_t* in, uint64_t in_bytes, const uint64_t* rec_off, const uint64_t* rec_idx,
+                            const uint64_t* n_dev, uint64_t n_capacity, uint8_t* block, uint64_t block_bytes,
+                            uint64_t start, uint64_t limit, uint32_t mtu, uint64_t max_message_length,
+                            const sbe_term_header* hdr, const sbe_term_append_out* o, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const uint64_t n = n_capacity;
+    if (!hdr || !o || !o->counts) return SBE_EINVAL;
+    if (n > 0 && (!rec_off || !in || !block || !workspace || !n_dev)) return SBE_EINVAL;
+    if ((block_bytes & 31) || (start & 31) || start > block_bytes || block_bytes > kTaMaxBlock) return SBE_EINVAL;
+    if ((mtu & 31) || mtu < 64 || mtu > 65504 || max_message_length > kTaMaxBlock) return SBE_EINVAL;
+    if (misaligned(block, 15) || misaligned(rec_off, 7) || misaligned(o->rec_tail, 7) || misaligned(o->counts, 7) ||
+        misaligned(rec_idx, 7) || (n > 0 && misaligned(n_dev, 7)))
+        return SBE_EINVAL;
+    if (n >= (1ull << 32)) return SBE_EINVAL;
+    if (n == 0) {
+        hipLaunchKernelGGL(ta_counts_only, dim3(1), dim3(1), 0, s, o->counts, start);
+        return record_hip(hipGetLastError());
+    }
+    if (workspace_bytes < sbe_term_append_workspace_size(n)) return SBE_ENOSPC;
+    const uint64_t nb = (n + 1 + kTaBlk - 1) / kTaBlk;
+    Carver ws(workspace);
+    TaArgs a{in, in_bytes, rec_off, n, block, block_bytes, start, limit, mtu, max_message_length, *hdr};
+    a.tails = ws.take<uint64_t>(n);
+    if (o->rec_tail) a.tails = o->rec_tail;
+    a.counts = o->counts;
+    a.bsum = ws.take<uint64_t>(nb);
+    a.bmin = ws.take<uint64_t>(nb);
+    a.plan = ws.take<TaPlan>(1);
+    const TaCount c{n_dev, TaIdx{rec_idx, n}};
+    hipLaunchKernelGGL(ta_sums_counted, dim3((uint32_t)nb), dim3(kTaBlk), 0, s, a, c);
+    hipLaunchKernelGGL(ta_scan_blocks, dim3(1), dim3(kTaBlk), 0, s, a, nb);
+    hipLaunchKernelGGL(ta_tails_counted, dim3((uint32_t)nb), dim3(kTaBlk), 0, s, a, c);
+    const uint32_t tile0 = (uint32_t)(start / kTaTile), nt = (uint32_t)((block_bytes + kTaTile - 1) / kTaTile) - tile0;
+    if (block_bytes > start) hipLaunchKernelGGL(ta_write_counted, dim3(nt), dim3(kTaThreads), 0, s, a, c, tile0);
     return record_hip(hipGetLastError());
 }
 

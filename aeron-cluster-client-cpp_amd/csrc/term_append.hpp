@@ -72,10 +72,26 @@ struct TaRec {
     bool bad, too_long;
     uint64_t req;  // 0 for a record that is bad or too long
 };
-__device__ __forceinline__ TaRec ta_rec(const TaArgs& a, uint64_t i) {
+// kIdx (sbe_term_append_counted): record i is rec_off[idx.at[i]] .. rec_off[idx.at[i] + 1] where
+// idx.at is not null; an index at or past the capacity (rec_off has capacity + 1 entries) is a bad record
+struct TaIdx {
+    const uint64_t* at;  // [capacity] or nullptr
+    uint64_t cap;
+};
+template <bool kIdx>
+__device__ __forceinline__ uint64_t ta_src(const TaIdx& idx, uint64_t i) {
+    return kIdx && idx.at ? idx.at[i] : i;
+}
+template <bool kIdx>
+__device__ __forceinline__ TaRec ta_rec(const TaArgs& a, const TaIdx& idx, uint64_t i) {
     TaRec r{0, false, false, 0};
     if (i >= a.n) return r;
-    const uint64_t lo = a.rec_off[i], hi = a.rec_off[i + 1];
+    const uint64_t s = ta_src<kIdx>(idx, i);
+    if (kIdx && s >= idx.cap) {
+        r.bad = true;
+        return r;
+    }
+    const uint64_t lo = a.rec_off[s], hi = a.rec_off[s + 1];
     r.bad = hi < lo || hi > a.in_bytes;
     if (r.bad) return r;
     r.len = hi - lo;
@@ -97,9 +113,10 @@ __device__ __forceinline__ uint64_t ta_block_min(uint64_t v) {
     return m;
 }
 
-__global__ __launch_bounds__(kTaBlk) void ta_sums(TaArgs a) {
+template <bool kIdx>
+__device__ __forceinline__ void ta_sums_block(const TaArgs& a, const TaIdx& idx) {
     const uint64_t i = (uint64_t)blockIdx.x * kTaBlk + threadIdx.x;
-    const TaRec r = ta_rec(a, i);
+    const TaRec r = ta_rec<kIdx>(a, idx, i);
     uint64_t tot;
     (void)mat_block_scan(r.req, tot);
     const uint64_t m = ta_block_min((r.bad || r.too_long) ? i : kTaNone);
@@ -108,6 +125,7 @@ __global__ __launch_bounds__(kTaBlk) void ta_sums(TaArgs a) {
         a.bmin[blockIdx.x] = m;
     }
 }
+__global__ __launch_bounds__(kTaBlk) void ta_sums(TaArgs a) { ta_sums_block<false>(a, TaIdx{}); }
 
 __global__ __launch_bounds__(kTaBlk) void ta_scan_blocks(TaArgs a, uint64_t nb) {
     uint64_t carry = 0, m = kTaNone;
@@ -127,11 +145,20 @@ __global__ __launch_bounds__(kTaBlk) void ta_scan_blocks(TaArgs a, uint64_t nb) 
     if (threadIdx.x == 0) a.plan->first_static = m;
 }
 
-__global__ __launch_bounds__(kTaBlk) void ta_tails(TaArgs a) {
+template <bool kIdx>
+__device__ __forceinline__ void ta_tails_block(const TaArgs& a, const TaIdx& idx) {
     const uint64_t i = (uint64_t)blockIdx.x * kTaBlk + threadIdx.x;
-    const TaRec r = ta_rec(a, i);
+    const TaRec r = ta_rec<kIdx>(a, idx, i);
     uint64_t tot;
     const uint64_t tb = a.start + a.bsum[blockIdx.x] + mat_block_scan(r.req, tot);  // the tail before record i
+    if (kIdx && idx.at) {
+        // the payload bytes: gathered records do not lie back to back, so the appended ones (those that
+        // no stop condition holds for) add their lengths up, one atomic a wave (ta_sums_counted zeroed it)
+        const uint64_t fs0 = a.plan->first_static;
+        const bool in = i < a.n && i < fs0 && tb < a.limit && tb + r.req <= a.block_bytes;
+        const uint64_t w = wave_sum64(in ? r.len : 0ull);
+        if ((threadIdx.x & (kWave - 1)) == 0 && w) atomicAdd(reinterpret_cast<unsigned long long*>(a.counts + 2), (unsigned long long)w);
+    }
     if (i > a.n) return;
     if (i < a.n) a.tails[i] = tb + r.req;
     const uint64_t fs = a.plan->first_static;
@@ -140,7 +167,7 @@ __global__ __launch_bounds__(kTaBlk) void ta_tails(TaArgs a) {
     const bool fails = i == a.n || i >= fs || tb >= a.limit || tb + r.req > a.block_bytes;
     bool prev = false;
     if (i > 0) {
-        const TaRec p = ta_rec(a, i - 1);
+        const TaRec p = ta_rec<kIdx>(a, idx, i - 1);
         prev = i - 1 >= fs || tb - p.req >= a.limit || tb > a.block_bytes;
     }
     if (!fails || prev) return;
@@ -155,9 +182,11 @@ __global__ __launch_bounds__(kTaBlk) void ta_tails(TaArgs a) {
     a.plan->pad = trip && tb < a.block_bytes ? 1u : 0u;
     a.counts[0] = i;
     a.counts[1] = trip ? a.block_bytes : tb;
-    a.counts[2] = a.rec_off[i] - a.rec_off[0];  // records 0..i-1 are well formed: the offsets up to i only grow
+    if (!(kIdx && idx.at))
+        a.counts[2] = a.rec_off[i] - a.rec_off[0];  // records 0..i-1 are well formed: the offsets up to i only grow
     a.counts[3] = stop;
 }
+__global__ __launch_bounds__(kTaBlk) void ta_tails(TaArgs a) { ta_tails_block<false>(a, TaIdx{}); }
 
 // 16 bytes of `in` from byte s on, of which the first v (1..16) are payload: the others are zero.
 // One unaligned load where all 16 lie inside `in`, bytewise at the very end of it.
@@ -177,9 +206,11 @@ __device__ __forceinline__ u32x4 ta_payload(const TaArgs& a, uint64_t s, uint32_
     return x;
 }
 
-__global__ __launch_bounds__(kTaThreads) void ta_write(TaArgs a, uint32_t tile0) {
+template <bool kIdx>
+__device__ __forceinline__ void ta_write_tile(const TaArgs& a, const TaIdx& idx, uint32_t tile0) {
     __shared__ uint32_t tail[kTaTileRecs + 2];  // tail[0]: the tail before the tile's first record; tail[k + 1]: behind record first + k
     __shared__ uint64_t src[kTaTileRecs + 2];   // rec_off[first + k]
+    __shared__ uint32_t slen[kIdx ? kTaTileRecs + 2 : 1];  // kIdx: the record's length (its neighbour's start says nothing)
     const uint64_t appended = a.plan->appended, data_end = a.plan->data_end;
     const uint64_t t0 = (uint64_t)(tile0 + blockIdx.x) * kTaTile;
     const uint64_t lo = t0 > a.start ? t0 : a.start;
@@ -208,7 +239,13 @@ __global__ __launch_bounds__(kTaThreads) void ta_write(TaArgs a, uint32_t tile0)
     for (uint32_t k = threadIdx.x; k <= cnt; k += kTaThreads) {
         const uint64_t j = first + k;
         tail[k] = (uint32_t)(j == 0 ? a.start : a.tails[j - 1]);
-        src[k] = a.rec_off[j];  // j <= appended <= n
+        if (!kIdx) {
+            src[k] = a.rec_off[j];  // j <= appended <= n
+        } else if (j < appended) {
+            const uint64_t s = ta_src<kIdx>(idx, j), at = a.rec_off[s];
+            src[k] = at;
+            slen[k] = (uint32_t)(a.rec_off[s + 1] - at);
+        }
     }
     __syncthreads();
     const uint32_t maxp = a.mtu - 32u;
@@ -237,7 +274,7 @@ __global__ __launch_bounds__(kTaThreads) void ta_write(TaArgs a, uint32_t tile0)
             }
             const uint32_t begin = tail[k], q = (uint32_t)p - begin;
             const uint64_t s0 = src[k];
-            const uint32_t L = (uint32_t)(src[k + 1] - s0);  // an appended record: at most max_message_length <= 2^30
+            const uint32_t L = kIdx ? slen[k] : (uint32_t)(src[k + 1] - s0);  // an appended record: at most max_message_length <= 2^30
             uint32_t f = 0, r = q, plen = L, flags = 0xC0u;
             if (L > maxp) {
                 f = q / a.mtu;
@@ -260,6 +297,36 @@ __global__ __launch_bounds__(kTaThreads) void ta_write(TaArgs a, uint32_t tile0)
         }
         __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(a.block + p));
     }
+}
+__global__ __launch_bounds__(kTaThreads) void ta_write(TaArgs a, uint32_t tile0) { ta_write_tile<false>(a, TaIdx{}, tile0); }
+
+// sbe_term_append_counted.  a.n is the capacity the plan grids and the block tables were laid out by;
+// every launch takes its count from *n_dev.  A plan block past the count leaves its sums empty for
+// the scan (which runs over the blocks of the capacity, ta_scan_blocks as it is) and exits; the
+// block that holds record n (the one behind the last) still runs the tails.
+struct TaCount {
+    const uint64_t* n_dev;
+    TaIdx idx;
+};
+__global__ __launch_bounds__(kTaBlk) void ta_sums_counted(TaArgs a, TaCount c) {
+    a.n = counted_n(c.n_dev, a.n);
+    if (c.idx.at && blockIdx.x == 0 && threadIdx.x == 0) a.counts[2] = 0;  // ta_tails_counted adds the payload bytes up
+    if ((uint64_t)blockIdx.x * kTaBlk >= a.n) {
+        if (threadIdx.x == 0) {
+            a.bsum[blockIdx.x] = 0;
+            a.bmin[blockIdx.x] = kTaNone;
+        }
+        return;
+    }
+    ta_sums_block<true>(a, c.idx);
+}
+__global__ __launch_bounds__(kTaBlk) void ta_tails_counted(TaArgs a, TaCount c) {
+    a.n = counted_n(c.n_dev, a.n);
+    if ((uint64_t)blockIdx.x * kTaBlk > a.n) return;
+    ta_tails_block<true>(a, c.idx);
+}
+__global__ __launch_bounds__(kTaThreads) void ta_write_counted(TaArgs a, TaCount c, uint32_t tile0) {
+    ta_write_tile<true>(a, c.idx, tile0);  // the plan holds what the count left: n is not read
 }
 
 // counts of a call without records

@@ -3199,6 +3199,190 @@ TermAppendResult TermAppender::append(const std::uint8_t* data, std::size_t nbyt
     return r;
 }
 
+EgressCommitter::EgressCommitter(std::string client_id, std::string fallback_topic)
+    : client_id_(std::move(client_id)), fallback_(std::move(fallback_topic)) {
+    if (fallback_.size() > SBE_COMMIT_TABLE_BYTES) throw std::length_error("EgressCommitter: fallback topic too long");
+}
+
+void EgressCommitter::set_message_identifier(const std::string& topic, const std::string& identifier) {
+    if (!identifiers_.count(topic)) {
+        size_t bytes = fallback_.size() + topic.size();
+        for (const auto& kv : identifiers_) bytes += kv.first.size();
+        if (identifiers_.size() + 2 > SBE_COMMIT_MAX_TOPICS || bytes > SBE_COMMIT_TABLE_BYTES)
+            throw std::length_error("EgressCommitter: the topic table holds 64 topics and 4096 bytes");
+    }
+    identifiers_[topic] = identifier;
+}
+
+EgressStepResult EgressCommitter::poll_commit_append(const std::uint8_t* block, std::size_t len, std::size_t start,
+                                                     std::uint8_t* ingress, std::size_t ingress_len, std::size_t ingress_start,
+                                                     const EgressStepOptions& options, EncodedBatch* messages) {
+    if ((len & 31) || (start & 31) || start > len)
+        throw std::invalid_argument("poll_commit_append: block and start are multiples of 32");
+    options.append.check(ingress_len, ingress_start);
+    const size_t body = len - start, carry_in = acc_.size(), bound = carry_in + body;
+    if (body > ((size_t)1 << 30) || bound > ((size_t)1 << 31)) throw std::invalid_argument("poll_commit_append: more than 2^30 bytes");
+    if (client_id_.size() > SBE_COMMIT_TABLE_BYTES) throw std::length_error("EgressCommitter: the default identifier holds 4096 bytes");
+    // the tables of AutoCommitter::run: the fallback topic, then the topics with an identifier
+    std::vector<const std::string*> table{&fallback_};
+    for (const auto& kv : identifiers_) table.push_back(&kv.first);
+    const uint32_t k = (uint32_t)table.size();
+    auto ident = [&](const std::string& t) -> const std::string& {
+        auto it = identifiers_.find(t);
+        return it == identifiers_.end() ? client_id_ : it->second;
+    };
+    size_t ident_bytes = 0, ident_max = client_id_.size();
+    for (const std::string* t : table) {
+        ident_bytes += ident(*t).size();
+        ident_max = std::max(ident_max, ident(*t).size());
+    }
+    if (ident_bytes > SBE_COMMIT_TABLE_BYTES) throw std::length_error("EgressCommitter: the identifier table holds 4096 bytes");
+    const uint64_t now_ns = options.clock ? options.clock() : now_nanos_sys();
+    const uint64_t uuid_ns = options.clock ? options.clock() : now_nanos_sys();
+
+    Ctx& c = ctx();
+    Pipeline::Slot& s = c.pipe.slot[0];  // as poll_term_block
+    hipStream_t stream = c.batch_stream();
+    const uint64_t lim = options.limit == ~(size_t)0 ? ~0ull : (uint64_t)options.limit;
+    const size_t cap = (size_t)(lim < body / 32 ? lim : body / 32);  // fragments, and so messages, at most
+    // staged tables: topic arena and offsets, topic ids, identifier arena and offsets, client_id
+    const size_t t_to = SBE_COMMIT_TABLE_BYTES, t_tid = t_to + al16(4 * (SBE_COMMIT_MAX_TOPICS + 1)),
+                 t_ia = t_tid + al16(4 * SBE_COMMIT_MAX_TOPICS), t_io = t_ia + SBE_COMMIT_TABLE_BYTES,
+                 t_di = t_io + al16(4 * (SBE_COMMIT_MAX_TOPICS + 1)), tables = t_di + SBE_COMMIT_TABLE_BYTES;
+    s.pin.need(tables);
+    uint8_t* hp = s.pin.b();
+    std::memset(hp, 0, tables);
+    uint32_t* to = reinterpret_cast<uint32_t*>(hp + t_to);
+    uint32_t* tid = reinterpret_cast<uint32_t*>(hp + t_tid);
+    uint32_t* io = reinterpret_cast<uint32_t*>(hp + t_io);
+    for (uint32_t j = 0; j < k; ++j) {
+        const std::string& id = ident(*table[j]);
+        std::memcpy(hp + to[j], table[j]->data(), table[j]->size());
+        to[j + 1] = to[j] + (uint32_t)table[j]->size();
+        tid[j] = CommitManager::topic_to_id(*table[j]);
+        std::memcpy(hp + t_ia + io[j], id.data(), id.size());
+        io[j + 1] = io[j] + (uint32_t)id.size();
+    }
+    std::memcpy(hp + t_di, client_id_.data(), client_id_.size());
+    // device input: the block as it is, the accumulator (the poll's carry), the tables
+    const size_t i_carry = al16(body), i_tab = al16(i_carry + carry_in);
+    s.d_in.need(i_tab + tables + 16);
+    uint8_t* di = s.d_in.b();
+    if (body) hip_check(hipMemcpyAsync(di, block + start, body, hipMemcpyHostToDevice, stream), "H2D");
+    if (carry_in) hip_check(hipMemcpyAsync(di + i_carry, acc_.data(), carry_in, hipMemcpyHostToDevice, stream), "H2D");
+    hip_check(hipMemcpyAsync(di + i_tab, hp, tables, hipMemcpyHostToDevice, stream), "H2D");
+    // device output, every per-record array sized by the capacity
+    const size_t n = cap, n1 = n ? n : 1;
+    const size_t frames_cap = (size_t)sbe_commit_fallback_output_bound(n, bound + n * ident_max, 1);
+    const size_t w_poll = sbe_term_poll_workspace_size(body, cap), w_emit = sbe_commit_emit_workspace_size(n),
+                 w_app = sbe_term_append_workspace_size(n);
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = at;
+        at = al16(at + bytes);
+        return o;
+    };
+    const size_t o_out = take(bound + 16), o_moff = take(8 * (n + 1)), o_pcnt = take(48), o_st = take(n1), o_fl = take(n1),
+                 o_hdr = take(8 * n1), o_ts = take(8 * n1), o_vo = take(20 * n1), o_vl = take(20 * n1), o_seq = take(8 * n1),
+                 p_cm = take(n1), p_src = take(n1), p_kind = take(n1), p_off = take(4 * n1), p_len = take(4 * n1),
+                 p_idx = take(4 * n1), p_last = take(8 * SBE_COMMIT_MAX_TOPICS), p_cnt = take(8 * (SBE_COMMIT_MAX_TOPICS + 2)),
+                 e_st = take(n1), e_off = take(8 * (n + 1)), e_idx = take(8 * n1), e_tot = take(32), a_tail = take(8 * n1),
+                 a_cnt = take(32), o_wp = take(w_poll + 16), o_we = take(w_emit + 16), o_wa = take(w_app + 16),
+                 o_frames = take(frames_cap + 16), o_blk = take(ingress_len + 16);
+    s.d_out.need(at);
+    uint8_t* d = s.d_out.b();
+    auto u64p = [&](size_t o) { return reinterpret_cast<uint64_t*>(d + o); };
+    auto u32p = [&](size_t o) { return reinterpret_cast<uint32_t*>(d + o); };
+    const sbe_term_poll_out po{u64p(o_moff), u64p(o_pcnt)};
+    if (sbe_term_poll(di, body, 0, lim, cap, carry_in ? di + i_carry : nullptr, carry_in, d + o_out, bound, &po, d + o_wp, w_poll,
+                      stream) != SBE_OK)
+        fail("sbe_term_poll");
+    const uint64_t* n_dev = po.counts + 4;  // the message count stays where the poll left it
+    const sbe_decoded dec{d + o_st, d + o_fl, reinterpret_cast<uint16_t*>(d + o_hdr), u64p(o_ts), u32p(o_vo), u32p(o_vl), u64p(o_seq)};
+    const sbe_commit_out plan{d + p_cm, d + p_src, d + p_kind, u32p(p_off), u32p(p_len), u32p(p_idx), u64p(p_last), u64p(p_cnt)};
+    const sbe_commit_fallback fb{di + i_tab, reinterpret_cast<const uint32_t*>(di + i_tab + t_to), di + i_tab + t_di,
+                                 (uint32_t)client_id_.size(), now_ns, uuid_ns};
+    const sbe_commit_emit_out res{u64p(e_off), d + e_st, u64p(e_idx), u64p(e_tot)};
+    const sbe_term_header h{options.append.header.session_id, options.append.header.stream_id, options.append.header.term_id,
+                            options.append.header.term_offset_base, options.append.header.version};
+    const sbe_term_append_out ao{u64p(a_tail), u64p(a_cnt)};
+    const bool ok =
+        sbe_decode_batch_counted(d + o_out, po.msg_off, n_dev, n, 0, SBE_DEC_PARSE_MESSAGE, &dec, stream) == SBE_OK &&
+        sbe_classify_commits_counted(d + o_out, po.msg_off, n_dev, n, &dec, di + i_tab, fb.topic_off, k, &plan, nullptr, 0,
+                                     stream) == SBE_OK &&
+        sbe_emit_commit_offsets_counted(d + o_out, po.msg_off, n_dev, n, &dec, &plan,
+                                        reinterpret_cast<const uint32_t*>(di + i_tab + t_tid), di + i_tab + t_ia,
+                                        reinterpret_cast<const uint32_t*>(di + i_tab + t_io), k, nullptr, 0, 1,
+                                        options.leadership_term_id, options.cluster_session_id, d + o_frames, frames_cap, &res,
+                                        d + o_we, w_emit, stream, &fb) == SBE_OK &&
+        sbe_term_append_counted(d + o_frames, frames_cap, res.out_off, res.emit_idx, res.totals, n, d + o_blk, ingress_len,
+                                ingress_start, options.append.limit, options.append.mtu,
+                                options.append.effective_max_message_length(ingress_len), &h, &ao, d + o_wa, w_app,
+                                stream) == SBE_OK;
+    if (!ok) {
+        c.abort_all();
+        fail("poll_commit_append");
+    }
+    c.h_aux.need(128);
+    uint64_t* hc = reinterpret_cast<uint64_t*>(c.h_aux.p);  // poll counts [6], totals [3] at 6, append counts [4] at 10
+    hip_check(hipMemcpyAsync(hc, po.counts, 48, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipMemcpyAsync(hc + 6, res.totals, 24, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipMemcpyAsync(hc + 10, ao.counts, 32, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");  // the one wait for the kernels: the two below are for downloads
+    EgressStepResult r;
+    std::memcpy(r.poll_counts, hc, 48);
+    r.next = start + (size_t)hc[1];
+    const size_t m = (size_t)hc[4], carry = (size_t)hc[5];
+    r.messages = m;
+    r.frames = hc[6];
+    r.frame_bytes = hc[7];
+    r.appended.appended = (size_t)hc[10];
+    r.appended.next = hc[11];
+    r.appended.stop = (uint32_t)hc[13];
+    if (hc[0] == 0) {  // no fragment: nothing delivered, the accumulator as it was
+        if (messages) {
+            *messages = EncodedBatch();
+            messages->offsets = HostBytesAccess::make<uint64_t>(1);
+            messages->offsets[0] = 0;
+        }
+        return r;
+    }
+    std::vector<uint8_t> st(m);
+    std::vector<uint64_t> moff(m + 1), fidx((size_t)r.frames);
+    r.appended.rec_tail.resize(r.appended.appended);
+    hip_check(hipMemcpyAsync(moff.data(), po.msg_off, 8 * (m + 1), hipMemcpyDeviceToHost, stream), "D2H");
+    if (m) hip_check(hipMemcpyAsync(st.data(), res.status, m, hipMemcpyDeviceToHost, stream), "D2H");
+    if (r.frames) hip_check(hipMemcpyAsync(fidx.data(), res.emit_idx, 8 * fidx.size(), hipMemcpyDeviceToHost, stream), "D2H");
+    if (r.appended.appended)
+        hip_check(hipMemcpyAsync(r.appended.rec_tail.data(), ao.rec_tail, 8 * r.appended.appended, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    const size_t msg_bytes = (size_t)moff[m];
+    acc_.resize(carry);
+    if (carry) hip_check(hipMemcpyAsync(acc_.data(), d + o_out + msg_bytes, carry, hipMemcpyDeviceToHost, stream), "D2H");
+    if (messages) {
+        *messages = EncodedBatch();
+        messages->offsets = HostBytesAccess::make<uint64_t>(m + 1);
+        std::memcpy(messages->offsets.data(), moff.data(), 8 * (m + 1));
+        messages->status = HostBytesAccess::make<uint8_t>(m);
+        HostBytesAccess::zero(messages->status);
+        messages->bytes = HostBytesAccess::make(msg_bytes);
+        if (msg_bytes) hip_check(hipMemcpyAsync(messages->bytes.data(), d + o_out, msg_bytes, hipMemcpyDeviceToHost, stream), "D2H");
+    }
+    // what the append wrote: the frames, and of a padding frame its header
+    const uint64_t data_end = r.appended.appended ? r.appended.rec_tail.back() : ingress_start;
+    const uint64_t end = data_end + (r.appended.stop == SBE_TERM_APPEND_TRIPPED && data_end < ingress_len ? 32 : 0);
+    if (end > ingress_start)
+        hip_check(hipMemcpyAsync(ingress + ingress_start, d + o_blk + ingress_start, end - ingress_start, hipMemcpyDeviceToHost, stream), "D2H");
+    hip_check(hipStreamSynchronize(stream), "sync");
+    r.frame_record.assign(fidx.begin(), fidx.end());
+    for (size_t i = 0; i < m; ++i) {
+        if (st[i] == SBE_CE_HOST) r.host.push_back(i);
+        else if (st[i] == SBE_CE_E109_MESSAGE_ID) r.too_long.push_back(i);
+        else if (st[i] == SBE_CE_E100_FALLBACK) r.fallback_e100.push_back(i);
+    }
+    return r;
+}
+
 MessageHandler::MessageHandler() = default;
 MessageHandler::~MessageHandler() = default;
 

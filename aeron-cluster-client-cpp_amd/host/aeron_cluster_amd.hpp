@@ -963,6 +963,58 @@ public:
                                   std::size_t start, const TermAppendOptions& options = {});
 };
 
+// The subscriber's egress step (polling_worker -> poll -> handle_incoming_message -> commit_message ->
+// send_commit_offset -> offer) as one enqueue: the raw egress block goes up once, sbe_term_poll and
+// the four *_counted calls (decode, classify, emit, term append) run back to back on the stream
+// with the message count and the frame count staying in device memory.  The host waits once for
+// the kernels (the counts come back with that wait); the downloads whose sizes the counts give
+// take two more waits, as poll_term_block's do: the offsets, statuses, frame records and tails,
+// then the carry, the messages and the bytes written to the ingress block.  The result is defined by the classes above: the ingress block holds what
+// TermAppender::append writes for the frames AutoCommitter::commit_and_send_batch (json_fallback,
+// session frames, no mask) offers for MessageParser's parse of FragmentReassembler::poll_term_block's
+// messages, but for the records the device leaves to the host (SBE_CE_HOST: escaped or non-string
+// topics), which are reported in `host` and not sent; `next` and the kept carry are
+// poll_term_block's.  The CommitManager is not touched: the caller commits from the messages.
+struct EgressStepOptions {
+    std::size_t limit = ~(std::size_t)0;  // fragments per poll
+    std::int64_t leadership_term_id = 0;
+    std::int64_t cluster_session_id = 0;
+    std::function<std::uint64_t()> clock;  // read twice, as CommitSendOptions::clock
+    TermAppendOptions append;
+};
+struct EgressStepResult {
+    std::uint64_t poll_counts[6] = {0, 0, 0, 0, 0, 0};  // sbe_term_poll's: fragments, next, payload bytes, stop, messages, carry
+    std::size_t next = 0;                  // where the poll stopped: the start of the next call
+    std::size_t messages = 0;
+    std::uint64_t frames = 0, frame_bytes = 0;  // the emit call's totals
+    TermAppendResult appended;             // of the commit frames; appended < frames: go on in the next term
+    std::vector<std::size_t> frame_record; // [frames] the message each frame commits, ascending
+    std::vector<std::size_t> host;         // messages left to the host (SBE_CE_HOST), ascending
+    std::vector<std::size_t> too_long;     // SBE_CE_E109_MESSAGE_ID
+    std::vector<std::size_t> fallback_e100;  // SBE_CE_E100_FALLBACK
+};
+class EgressCommitter {
+public:
+    explicit EgressCommitter(std::string client_id, std::string fallback_topic = "default");
+    // as AutoCommitter::set_message_identifier (std::length_error beyond 63 topics or 4096 bytes)
+    void set_message_identifier(const std::string& topic, const std::string& identifier);
+    // One step over block[start, len) into ingress[ingress_start, ingress_len).  `messages`, when
+    // given, receives the polled messages (what poll_term_block returns), for the records in `host`.
+    // Throws what the composed calls throw: std::invalid_argument for a block, start, ingress
+    // length or ingress start that is no multiple of 32, a start behind its block, more than 2^30
+    // bytes, a bad mtu or max_message_length (TermAppendOptions::check); std::length_error when the
+    // identifiers or client_id exceed 4096 bytes.
+    EgressStepResult poll_commit_append(const std::uint8_t* block, std::size_t len, std::size_t start, std::uint8_t* ingress,
+                                        std::size_t ingress_len, std::size_t ingress_start,
+                                        const EgressStepOptions& options = {}, EncodedBatch* messages = nullptr);
+    std::size_t pending_bytes() const { return acc_.size(); }
+
+private:
+    std::string client_id_, fallback_;
+    std::map<std::string, std::string> identifiers_;
+    std::vector<std::uint8_t> acc_;
+};
+
 // include/aeron_cluster/order_types.hpp:16-66: the members Order::to_json, Order::validate and
 // publish_order read (the reference class carries more; they play no part in either).
 struct Order {

@@ -320,6 +320,22 @@ def _load():
                                     ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                     ctypes.POINTER(_TermHeader), ctypes.POINTER(_TermAppendOut), ctypes.c_void_p,
                                     ctypes.c_size_t, ctypes.c_void_p]
+    if hasattr(lib, "sbe_decode_batch_counted"):  # record counts held in device memory
+        lib.sbe_decode_batch_counted.restype = ctypes.c_int
+        lib.sbe_decode_batch_counted.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                 ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(_Decoded),
+                                                 ctypes.c_void_p]
+        lib.sbe_classify_commits_counted.restype = ctypes.c_int
+        lib.sbe_classify_commits_counted.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                     ctypes.POINTER(_Decoded), ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_uint32, ctypes.POINTER(_CommitOut), ctypes.c_void_p,
+                                                     ctypes.c_size_t, ctypes.c_void_p]
+        lib.sbe_emit_commit_offsets_counted.restype = ctypes.c_int
+        a = list(lib.sbe_emit_commit_offsets_ex.argtypes)  # n -> n_dev, n_capacity
+        lib.sbe_emit_commit_offsets_counted.argtypes = a[:2] + [ctypes.c_void_p, ctypes.c_uint64] + a[3:]
+        lib.sbe_term_append_counted.restype = ctypes.c_int
+        a = list(lib.sbe_term_append.argtypes)  # n -> rec_idx, n_dev, n_capacity
+        lib.sbe_term_append_counted.argtypes = a[:3] + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64] + a[4:]
     lib.sbe_inflight_list_workspace_size.restype = ctypes.c_size_t
     lib.sbe_inflight_list_workspace_size.argtypes = [ctypes.c_uint32]
     lib.sbe_inflight_list_keys.restype = ctypes.c_int
@@ -1774,6 +1790,291 @@ def term_append(block, data, rec_off, start=0, limit=None, mtu=1408, max_message
                                ctypes.byref(h), ctypes.byref(o), _ptr(workspace), workspace.numel(), _stream(stream))
     _check(rc, "sbe_term_append")
     return TermAppended(block, None if rec_tail is None else rec_tail[:n], counts)
+
+
+# ---- record counts held in device memory (sbe_*_counted) ----
+# Each call takes n = min(count[0], capacity) records, where count is a one-element int64 device
+# tensor (or a view such as polled.counts[4:5] or frames.totals[0:1]) that an earlier call on the
+# same stream may still be writing; capacity sizes every array.  Nothing is read back: the results
+# keep their capacity-sized tensors, of which the first n entries are written.
+
+def _count(count, capacity, what):
+    count = _dev(count, torch.int64, "count")
+    if count.numel() < 1:
+        raise SbeError(f"{what}: count must hold one int64 element")
+    capacity = int(capacity)
+    if capacity < 0:
+        raise SbeError(f"{what}: capacity must not be negative")
+    return count, capacity
+
+
+def _counted_lib(what):
+    if not hasattr(lib(), "sbe_decode_batch_counted"):
+        raise SbeError(f"this libsbecodec.so has no {what}")
+    return lib()
+
+
+def decode_batch_counted(data, rec_off, count, capacity, mode=DEC_PARSE_MESSAGE, out: Decoded | None = None,
+                         stream=None, seq=None, avg_record_bytes: int = 0) -> Decoded:
+    """decode_batch over min(count[0], capacity) records: rec_off holds capacity + 1 offsets, out (and
+    seq) capacity records.  avg_record_bytes: the records' average size where the caller knows it;
+    only picks the kernel shape."""
+    L = _counted_lib("sbe_decode_batch_counted")
+    data = _dev(data, torch.uint8, "data")
+    rec_off = _dev(rec_off, torch.int64, "rec_off")
+    count, cap = _count(count, capacity, "decode_batch_counted")
+    if rec_off.numel() < cap + 1:
+        raise SbeError("decode_batch_counted: rec_off holds fewer than capacity + 1 offsets")
+    if out is None:
+        out = alloc_decoded(cap, data.device)
+    elif out.status.numel() < cap:
+        raise SbeError("decode_batch_counted: out holds fewer than capacity records")
+    if seq is True:
+        seq = torch.zeros(max(cap, 1), dtype=torch.int64, device=data.device)
+    if seq is not None and _dev(seq, torch.int64, "seq").numel() < cap:
+        raise SbeError("decode_batch_counted: seq holds fewer than capacity records")
+    d = _Decoded(*(getattr(out, k).data_ptr() for k in ("status", "flags", "hdr", "ts", "view_off", "view_len")),
+                 None if seq is None else seq.data_ptr())
+    rc = L.sbe_decode_batch_counted(_ptr(data), _ptr(rec_off), _ptr(count), cap, int(avg_record_bytes), mode,
+                                    ctypes.byref(d), _stream(stream))
+    _check(rc, "sbe_decode_batch_counted")
+    out = Decoded(*(getattr(out, k) for k in ("status", "flags", "hdr", "ts", "view_off", "view_len")))
+    out.seq = seq
+    return out
+
+
+def classify_commits_counted(data, rec_off, count, capacity, dec: Decoded, topics, out: CommitPlan | None = None,
+                             stream=None) -> CommitPlan:
+    """classify_commits over min(count[0], capacity) records of a decode_batch_counted result."""
+    L = _counted_lib("sbe_classify_commits_counted")
+    data = _dev(data, torch.uint8, "data")
+    rec_off = _dev(rec_off, torch.int64, "rec_off")
+    count, cap = _count(count, capacity, "classify_commits_counted")
+    if rec_off.numel() < cap + 1 or dec.status.numel() < cap:
+        raise SbeError("classify_commits_counted: rec_off / dec hold fewer than capacity records")
+    dev = data.device
+    arena, off = topics if isinstance(topics, tuple) else commit_topic_table(topics, dev)
+    arena = _dev(arena, torch.uint8, "topic arena")
+    off = _dev(off, torch.int32, "topic offsets")
+    if arena.numel() < COMMIT_TABLE_BYTES:
+        raise SbeError(f"the topic arena must hold {COMMIT_TABLE_BYTES} bytes")
+    k = int(off.numel()) - 1
+    if out is None:
+        m = max(cap, 1)
+        out = CommitPlan(*(torch.empty(m, dtype=t, device=dev) for t in
+                           (torch.uint8, torch.uint8, torch.uint8, torch.int32, torch.int32, torch.int32)),
+                         torch.empty(max(k, 1), dtype=torch.int64, device=dev),
+                         torch.empty(max(k, 1) + 2, dtype=torch.int64, device=dev))
+    elif out.cm.numel() < cap:
+        raise SbeError("classify_commits_counted: out holds fewer than capacity records")
+    d = _Decoded(*(getattr(dec, f).data_ptr() for f in ("status", "flags", "hdr", "ts", "view_off", "view_len")))
+    o = _CommitOut(*(getattr(out, f).data_ptr() for f, _ in _COMMIT_KEYS))
+    rc = L.sbe_classify_commits_counted(_ptr(data), _ptr(rec_off), _ptr(count), cap, ctypes.byref(d), _ptr(arena),
+                                        _ptr(off), k, ctypes.byref(o), None, 0, _stream(stream))
+    _check(rc, "sbe_classify_commits_counted")
+    return out
+
+
+def emit_commit_offsets_counted(data, rec_off, count, capacity, dec: Decoded, plan: CommitPlan, topic_ids,
+                                identifiers, out, mask=None, flags=0, session=True, leadership_term_id=0,
+                                cluster_session_id=0, out_capacity=None, out_off=None, status=None, emit_idx=None,
+                                totals=None, workspace=None, stream=None,
+                                fallback: CommitFallback | None = None) -> CommitFrames:
+    """emit_commit_offsets over min(count[0], capacity) records.  out is the caller's (None with
+    out_capacity=0 only sizes): its bound depends on the capacity, not on the count.  topic_ids,
+    identifiers and the fallback's tables as emit_commit_offsets takes them; device pairs are used
+    as they are."""
+    L = _counted_lib("sbe_emit_commit_offsets_counted")
+    data = _dev(data, torch.uint8, "data")
+    rec_off = _dev(rec_off, torch.int64, "rec_off")
+    count, cap_n = _count(count, capacity, "emit_commit_offsets_counted")
+    if rec_off.numel() < cap_n + 1 or dec.status.numel() < cap_n or plan.cm.numel() < cap_n:
+        raise SbeError("emit_commit_offsets_counted: rec_off / dec / plan hold fewer than capacity records")
+    dev = data.device
+    if isinstance(topic_ids, torch.Tensor):
+        topic_ids = _dev(topic_ids, torch.int32, "topic_ids")
+    else:
+        import numpy as np
+        topic_ids = torch.from_numpy(np.asarray(list(topic_ids), np.uint32).view(np.int32)).to(dev)
+    k = int(topic_ids.numel())
+    arena, off = identifiers if isinstance(identifiers, tuple) else commit_identifier_table(identifiers, dev)
+    arena = _dev(arena, torch.uint8, "identifier arena")
+    off = _dev(off, torch.int32, "identifier offsets")
+    if arena.numel() < COMMIT_TABLE_BYTES:
+        raise SbeError(f"the identifier arena must hold {COMMIT_TABLE_BYTES} bytes")
+    if off.numel() != k + 1:
+        raise SbeError("identifiers and topic_ids must have one entry per topic-table entry")
+    mask = _dev(mask, torch.uint8, "mask")
+    if mask is not None and mask.numel() < cap_n:
+        raise SbeError("mask is shorter than the capacity")
+    fb = None
+    if fallback is not None:
+        t = fallback.topic_table
+        fb_arena, fb_off = t if isinstance(t, tuple) else commit_topic_table(t, dev)
+        fb_arena = _dev(fb_arena, torch.uint8, "fallback topic arena")
+        fb_off = _dev(fb_off, torch.int32, "fallback topic offsets")
+        if fb_arena.numel() < COMMIT_TABLE_BYTES or fb_off.numel() != k + 1:
+            raise SbeError("the fallback's topic table must be the classify call's table")
+        fb_ident = fallback.default_identifier
+        if not isinstance(fb_ident, torch.Tensor):
+            import numpy as np
+            fb_ident = torch.from_numpy(np.frombuffer(bytes(fb_ident), np.uint8).copy()).to(dev)
+        fb_ident = _dev(fb_ident, torch.uint8, "default identifier")
+        fb_ident_ptr = fb_ident if fb_ident.numel() else torch.zeros(16, dtype=torch.uint8, device=dev)
+        fb = _CommitFallback(fb_arena.data_ptr(), fb_off.data_ptr(), fb_ident_ptr.data_ptr(), int(fb_ident.numel()),
+                             int(fallback.now_ns) & (2**64 - 1), int(fallback.uuid_ns) & (2**64 - 1))
+    out = _dev(out, torch.uint8, "out")
+    cap = 0 if out is None else int(out.numel()) if out_capacity is None else int(out_capacity)
+    if out is None and cap:
+        raise SbeError("emit_commit_offsets_counted: out_capacity without out")
+    if out is not None and cap > out.numel():
+        raise SbeError(f"out_capacity {cap} exceeds the out tensor ({out.numel()} bytes)")
+    m = max(cap_n, 1)
+    out_off = torch.empty(cap_n + 1, dtype=torch.int64, device=dev) if out_off is None else _dev(out_off, torch.int64, "out_off")
+    status = torch.empty(m, dtype=torch.uint8, device=dev) if status is None else _dev(status, torch.uint8, "status")
+    emit_idx = torch.empty(m, dtype=torch.int64, device=dev) if emit_idx is None else _dev(emit_idx, torch.int64, "emit_idx")
+    totals = torch.empty(3, dtype=torch.int64, device=dev) if totals is None else _dev(totals, torch.int64, "totals")
+    if out_off.numel() < cap_n + 1 or status.numel() < cap_n or emit_idx.numel() < cap_n or totals.numel() < 3:
+        raise SbeError("out_off / status / emit_idx / totals are shorter than the capacity")
+    need = commit_emit_workspace_size(cap_n)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    d = _Decoded(*(getattr(dec, f).data_ptr() for f in ("status", "flags", "hdr", "ts", "view_off", "view_len")),
+                 None if dec.seq is None else _dev(dec.seq, torch.int64, "dec.seq").data_ptr())
+    p = _CommitOut(*(getattr(plan, f).data_ptr() for f, _ in _COMMIT_KEYS))
+    r = _CommitEmitOut(out_off.data_ptr(), status.data_ptr(), emit_idx.data_ptr(), totals.data_ptr())
+    rc = L.sbe_emit_commit_offsets_counted(
+        _ptr(data), _ptr(rec_off), _ptr(count), cap_n, ctypes.byref(d), ctypes.byref(p), _ptr(topic_ids), _ptr(arena),
+        _ptr(off), k, _ptr(mask), int(flags), 1 if session else 0, int(leadership_term_id), int(cluster_session_id),
+        _ptr(out), cap, ctypes.byref(r), _ptr(workspace), workspace.numel(), _stream(stream),
+        None if fb is None else ctypes.byref(fb))
+    _check(rc, "sbe_emit_commit_offsets_counted")
+    return CommitFrames(out, out_off, status, emit_idx, totals, workspace)
+
+
+def term_append_counted(block, data, rec_off, count, capacity, rec_idx=None, data_bytes=None, start=0, limit=None,
+                        mtu=1408, max_message_length=None, header=TermHeader(), stream=None, workspace=None,
+                        rec_tail=None, want_tail=True, counts=None) -> TermAppended:
+    """term_append over min(count[0], capacity) records, where record j is data[rec_off[r]:rec_off[r+1]]
+    with r = rec_idx[j] (int64 [capacity]) or j.  With a CommitFrames f of capacity records,
+    term_append_counted(block, f.out, f.out_off, f.totals[0:1], capacity, rec_idx=f.emit_idx) appends
+    exactly the emitted frames.  data_bytes: the bytes of data that hold records (default: all)."""
+    L = _counted_lib("sbe_term_append_counted")
+    block = _dev(block, torch.uint8, "block")
+    data = _dev(data, torch.uint8, "data")
+    rec_off = _dev(rec_off, torch.int64, "rec_off")
+    rec_idx = _dev(rec_idx, torch.int64, "rec_idx")
+    count, cap = _count(count, capacity, "term_append_counted")
+    nb = int(block.numel())
+    dev = block.device
+    start = int(start)
+    if start < 0 or start > nb or (limit is not None and int(limit) < 0):
+        raise SbeError("term_append_counted: start must lie in [0, block.numel()], limit must not be negative")
+    if rec_off.numel() < cap + 1 or (rec_idx is not None and rec_idx.numel() < cap):
+        raise SbeError("term_append_counted: rec_off / rec_idx hold fewer than capacity records")
+    nd = int(data.numel()) if data_bytes is None else int(data_bytes)
+    if nd < 0 or nd > data.numel():
+        raise SbeError("term_append_counted: data_bytes exceeds the data tensor")
+    if max_message_length is None:
+        max_message_length = min(nb // 8, 16 << 20)
+    if not want_tail:
+        rec_tail = None
+    elif rec_tail is None:
+        rec_tail = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+    elif _dev(rec_tail, torch.int64, "rec_tail").numel() < cap:
+        raise SbeError("term_append_counted: rec_tail holds fewer than capacity elements")
+    if counts is None:
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+    elif _dev(counts, torch.int64, "counts").numel() < 4:
+        raise SbeError("term_append_counted: counts holds fewer than 4 elements")
+    need = int(L.sbe_term_append_workspace_size(cap))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    h = _TermHeader(int(header.session_id), int(header.stream_id), int(header.term_id), int(header.term_offset_base),
+                    int(header.version))
+    o = _TermAppendOut(None if rec_tail is None else rec_tail.data_ptr(), counts.data_ptr())
+    rc = L.sbe_term_append_counted(_ptr(data if data.numel() else workspace), nd, _ptr(rec_off), _ptr(rec_idx),
+                                   _ptr(count), cap, _ptr(block if nb else workspace), nb, start,
+                                   (1 << 64) - 1 if limit is None else int(limit), int(mtu), int(max_message_length),
+                                   ctypes.byref(h), ctypes.byref(o), _ptr(workspace), workspace.numel(),
+                                   _stream(stream))
+    _check(rc, "sbe_term_append_counted")
+    return TermAppended(block, rec_tail, counts)
+
+
+@dataclass
+class EgressStep:
+    """What egress_commit_step enqueued; every tensor is capacity-sized and still being written."""
+    polled: TermMessages
+    decoded: Decoded
+    plan: CommitPlan
+    frames: CommitFrames
+    appended: TermAppended
+
+
+def egress_commit_step(block, start, carry, topics, topic_ids, identifiers, ingress_block, ingress_start=0,
+                       limit=None, capacity=None, frames_out=None, fallback: CommitFallback | None = None, mask=None,
+                       flags=0, leadership_term_id=0, cluster_session_id=0, ingress_limit=None, mtu=1408,
+                       max_message_length=None, header=TermHeader(), avg_record_bytes=0, stream=None,
+                       bufs: EgressStep | None = None) -> EgressStep:
+    """The subscriber's egress step as one enqueue: term_poll of the raw egress block, then the
+    counted decode, classify, emit and term append of the commit frames into ingress_block, all on
+    one stream, the message count and the frame count staying in device memory (polled.counts[4],
+    frames.totals[0]).  Returns the result objects unsynchronised.  capacity: the most messages a
+    poll can deliver (default: term_poll's); frames_out: the uint8 buffer of the commit frames
+    (default: allocated at the output bound of `capacity` records, which needs `identifiers` as a
+    list of bytes); bufs: the EgressStep of an earlier call, whose tensors are then written again
+    (its polled.out must not hold this call's carry: copy the carry out first)."""
+    block = _dev(block, torch.uint8, "block")
+    dev = block.device
+    nb, start = int(block.numel()), int(start)
+    nc = 0 if carry is None else int(carry.numel())
+    if capacity is None:
+        capacity = (nb - start) // 32 + 1
+        if limit is not None:
+            capacity = min(capacity, int(limit))
+    capacity = int(capacity)
+    b = bufs
+    polled = term_poll(block, start=start, limit=limit, carry=carry, capacity=capacity, stream=stream,
+                       out=None if b is None else b.polled.out, msg_off=None if b is None else b.polled.msg_off,
+                       counts=None if b is None else b.polled.counts)
+    n_dev = polled.counts[4:5]
+    if b is None:
+        seq = torch.zeros(max(capacity, 1), dtype=torch.int64, device=dev)
+    else:
+        seq = b.decoded.seq
+    dec = decode_batch_counted(polled.out, polled.msg_off, n_dev, capacity, mode=DEC_PARSE_MESSAGE,
+                               out=None if b is None else b.decoded, stream=stream, seq=seq,
+                               avg_record_bytes=avg_record_bytes)
+    plan = classify_commits_counted(polled.out, polled.msg_off, n_dev, capacity, dec, topics,
+                                    out=None if b is None else b.plan, stream=stream)
+    if frames_out is None and b is not None:
+        frames_out = b.frames.out
+    if frames_out is None:
+        if isinstance(identifiers, tuple):
+            raise SbeError("egress_commit_step: frames_out is needed when identifiers is a device pair")
+        longest = max((len(bytes(t)) for t in identifiers), default=0)
+        if fallback is not None and not isinstance(fallback.default_identifier, torch.Tensor):
+            longest = max(longest, len(bytes(fallback.default_identifier)))
+        elif fallback is not None:
+            longest = max(longest, int(fallback.default_identifier.numel()))
+        bound = commit_emit_output_bound if fallback is None else commit_fallback_output_bound
+        frames_out = torch.empty(max(bound(capacity, nc + nb - start + capacity * min(longest, COMMIT_TABLE_BYTES), True), 16),
+                                 dtype=torch.uint8, device=dev)
+    f = None if b is None else b.frames
+    frames = emit_commit_offsets_counted(polled.out, polled.msg_off, n_dev, capacity, dec, plan, topic_ids, identifiers,
+                                         frames_out, mask=mask, flags=flags, session=True,
+                                         leadership_term_id=leadership_term_id, cluster_session_id=cluster_session_id,
+                                         out_off=None if f is None else f.out_off, status=None if f is None else f.status,
+                                         emit_idx=None if f is None else f.emit_idx,
+                                         totals=None if f is None else f.totals,
+                                         workspace=None if f is None else f.workspace, stream=stream, fallback=fallback)
+    a = None if b is None else b.appended
+    appended = term_append_counted(ingress_block, frames.out, frames.out_off, frames.totals[0:1], capacity,
+                                   rec_idx=frames.emit_idx, start=ingress_start, limit=ingress_limit, mtu=mtu,
+                                   max_message_length=max_message_length, header=header, stream=stream,
+                                   rec_tail=None if a is None else a.rec_tail, counts=None if a is None else a.counts)
+    return EgressStep(polled, dec, plan, frames, appended)
 
 
 # bytes per order of the default output bound (a record is at most ~800 B plus its escaped strings:

@@ -1182,6 +1182,57 @@ int sbe_term_append(const uint8_t* in, uint64_t in_bytes, const uint64_t* rec_of
                     const sbe_term_header* hdr, const sbe_term_append_out* o, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* ================== Record counts held in device memory (the *_counted calls) ================== */
+/* The subscriber's egress step (polling_worker -> poll -> handle_incoming_message -> commit_message
+ * -> send_commit_offset -> offer) without a host read between its stages: sbe_term_poll leaves its
+ * message count in counts[4], the emit call its frame count in totals[0], and the calls below take
+ * their record count from such a word.  The same rule in all four:
+ *   n = min(*n_dev, n_capacity)
+ * n_dev: a device const uint64_t*, 8-B aligned, read on `stream` by the launches that use it, so it
+ * may be the output of an earlier launch on that stream.  n_capacity (host) lays out the grids, the
+ * workspace and the block-sum tables: every array holds n_capacity records (rec_off n_capacity + 1
+ * offsets), the workspace is the base call's *_workspace_size(n_capacity).
+ * Results are those of the base call for n records.  No output element at a record index >= n is
+ * written and no input element at a record index >= n is read: rec_off[n] is the last offset read,
+ * rec_idx[j] is read for j < n only.  *n_dev == 0 is the base call's n == 0 (counts, totals,
+ * out_off[0], last and count are written; the launches are those of n_capacity > 0).  n_capacity ==
+ * 0: SBE_OK, the base call's n == 0 launch or memsets, n_dev is not read.  SBE_EINVAL (before
+ * anything touches a device, and before SBE_ENOSPC): whatever the base call refuses with n =
+ * n_capacity; a null or misaligned n_dev with n_capacity > 0; a misaligned rec_idx.  No call waits,
+ * copies to the host or allocates.  A workgroup past the count exits behind one scalar load.
+ *
+ * sbe_decode_batch_counted: sbe_decode_batch_sized.  avg_record_bytes picks the window by that call's
+ * thresholds on the average record size (0: the 16 KiB kernel); outputs are identical for any value.
+ * out->seq is evaluated in the same launch.
+ * sbe_classify_commits_counted: sbe_classify_commits; last and count are initialised by the call.
+ * sbe_emit_commit_offsets_counted: sbe_emit_commit_offsets_ex (fb == NULL: sbe_emit_commit_offsets):
+ * out_off[0..n], status[0..n), emit_idx[0..totals[0]) and totals.
+ * sbe_term_append_counted: sbe_term_append over n records, where record j is in[rec_off[r] ..
+ * rec_off[r + 1]) with r = rec_idx ? rec_idx[j] : j (rec_idx: device u64[n_capacity] or NULL; an r >=
+ * n_capacity is a bad record).  rec_tail[j] and counts keep their meaning, indexed by j (with rec_idx
+ * the payload bytes are added up with atomics).  With rec_off = res->out_off, rec_idx =
+ * res->emit_idx, n_dev = res->totals and in_bytes = the emit call's out_capacity it appends exactly the
+ * emitted frames: a frame reported SBE_CE_OVERFLOW ends past in_bytes, so it stops the append with
+ * SBE_TERM_APPEND_BAD_RECORD, is not consumed, and nothing outside `in` is read. */
+int sbe_decode_batch_counted(const uint8_t* in, const uint64_t* rec_off, const uint64_t* n_dev, uint64_t n_capacity,
+                             uint64_t avg_record_bytes, uint32_t mode, const sbe_decoded* out, void* stream);
+int sbe_classify_commits_counted(const uint8_t* in, const uint64_t* rec_off, const uint64_t* n_dev, uint64_t n_capacity,
+                                 const sbe_decoded* dec, const uint8_t* topic_arena, const uint32_t* topic_off,
+                                 uint32_t k, const sbe_commit_out* out, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int sbe_emit_commit_offsets_counted(const uint8_t* in, const uint64_t* rec_off, const uint64_t* n_dev,
+                                    uint64_t n_capacity, const sbe_decoded* dec, const sbe_commit_out* plan,
+                                    const uint32_t* topic_id, const uint8_t* ident_arena, const uint32_t* ident_off,
+                                    uint32_t k, const uint8_t* mask, uint32_t flags, int session,
+                                    int64_t leadership_term_id, int64_t cluster_session_id, uint8_t* out,
+                                    uint64_t out_capacity, const sbe_commit_emit_out* res, void* workspace,
+                                    size_t workspace_bytes, void* stream, const sbe_commit_fallback* fb);
+int sbe_term_append_counted(const uint8_t* in, uint64_t in_bytes, const uint64_t* rec_off, const uint64_t* rec_idx,
+                            const uint64_t* n_dev, uint64_t n_capacity, uint8_t* block, uint64_t block_bytes,
+                            uint64_t start, uint64_t limit, uint32_t mtu, uint64_t max_message_length,
+                            const sbe_term_header* hdr, const sbe_term_append_out* o, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* ========================== Order JSON (publish_order payload) ========================== */
 /* Replaces Order::to_json (src/order_types.cpp:122-181, jsoncpp StreamWriterBuilder with
  * indentation "" → compact, keys sorted) and the headers JSON publish_order builds beside it

@@ -36,6 +36,11 @@ algorithmic bytes per launch (computed from the actual record sizes) and its fra
                          term-buffer block with Aeron's framing at MTU 1408 on the device (sbe_term_append),
                          a device copy of the same payload bytes as the ceiling, and the host mirror's
                          one-thread term_append
+  egress_step            a raw 16 MiB block of session-framed fixed-256 Orders through the whole egress step
+                         (poll, decode, classify, emit, append of the commit frames): egress_commit_step as
+                         one enqueue with the counts on the device, and the uncounted calls with their two
+                         host reads on the same inputs; then sbe_decode_batch_counted beside
+                         sbe_decode_batch_sized on 1 M records at count == capacity and capacity / 16
   ack_correlate          1 M "pub_<nanos>" uuids remembered in a 2 M-slot in-flight table, then 1 M full
                          acks (about 10 % unknown ids, 1 % repeated ids) decoded on-egress and matched;
                          remember, match and the decode of the same ack batch timed in the same run, and
@@ -855,6 +860,133 @@ def row_term_append(steps, warmup):
     line("term_append", n, ms_app * 1e-3, {"sbe_term_append (4 launches)": (ms_app, nbytes)})
 
 
+def _wall_ms(fn, steps, warmup):
+    """Wall clock per call, the stream drained at both ends: for paths whose host reads are part of the cost."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def row_egress_step(steps, warmup):
+    """The subscriber's egress step on a raw 16 MiB term-buffer block of session-framed fixed-256
+    Orders (one BEGIN|END frame each, every header naming a known topic, so every message commits):
+    term poll, decode, classify, emit, term append of the commit frames into an ingress block.
+    Counted: egress_commit_step, one enqueue, the message count and the frame count staying on the
+    device.  Staged (the baseline, the path before the counted calls): the same kernels through the
+    uncounted calls, the host reading counts[4] before the decode and totals[0] before it builds the
+    frame table (two device ops) for the append.  Both in one process on the same rotated inputs,
+    wall clock per step with the stream drained at the end of the timed loop, the staged form measured
+    again behind the counted one.  Then, on 1 M fixed-256 records: sbe_decode_batch_counted at count ==
+    capacity against sbe_decode_batch_sized at that n, and at count == capacity / 16 against the sized
+    call at that n (what the empty tail of the grid costs), device events."""
+    import termscan_lib as S
+    total = 16 << 20
+    per = 32 + 32 + 256
+    nmsg = (total - 64) // per
+    arena, L, ts = T.fixed256_orders(nmsg)
+    a2 = arena.reshape(nmsg, 222).copy()
+    a2[:, 190:] = np.frombuffer(b'{"topic":"orders","a":"CREATE"} ', np.uint8)
+    data, off = T.oracle_encode_session(a2.reshape(-1), L, ts, 7, 9)[:2]
+    assert int(off[nmsg]) == nmsg * 288
+    b = S.Block()
+    for i in range(nmsg):
+        b.frame(bytes(data[288 * i: 288 * (i + 1)]), S.BEGIN | S.ENDF)
+    b.pad_to(total)
+    blk = b.bytes()
+    topics = [b"orders", b"order_request_topic", b"order_notification_topic"]
+    idents = [b"client-01", b"sub-req", b"sub-ntf"]
+    table = sbecodec.commit_topic_table(topics, "cuda")
+    itab = sbecodec.commit_identifier_table(idents, "cuda")
+    tid = dev(np.array([3, 1, 2], np.uint32), torch.int32)
+    d0 = torch.from_numpy(np.frombuffer(blk, np.uint8).copy()).cuda()
+    cap = nmsg + 1
+    kw = dict(leadership_term_id=7, cluster_session_id=9)
+    ing_bytes = 32 << 20
+
+    def make(k):
+        d = d0.clone()
+        ing = torch.empty(ing_bytes, dtype=torch.uint8, device="cuda")
+        s = sbecodec.egress_commit_step(d, 0, None, table, tid, idents, ing, capacity=cap, avg_record_bytes=288, **kw)
+        return d, ing, s
+
+    R = Rot(make)
+    torch.cuda.synchronize()
+    s0 = R.sets[0][2]
+    assert int(s0.polled.counts[4]) == nmsg and int(s0.frames.totals[0]) == nmsg
+    assert int(s0.appended.counts[0]) == nmsg and int(s0.appended.counts[3]) == sbecodec.TERM_APPEND_END
+    pws = torch.empty(int(sbecodec.lib().sbe_term_poll_workspace_size(total, cap)), dtype=torch.uint8, device="cuda")
+
+    def counted():
+        d, ing, s = R.next()
+        sbecodec.egress_commit_step(d, 0, None, table, tid, itab, ing, capacity=cap, avg_record_bytes=288, bufs=s, **kw)
+
+    def staged():
+        d, ing, s = R.next()
+        p = sbecodec.term_poll(d, capacity=cap, out=s.polled.out, msg_off=s.polled.msg_off, counts=s.polled.counts, workspace=pws)
+        m = int(p.counts[4])  # host read 1
+        ro = p.msg_off[: m + 1]
+        dec = sbecodec.decode_batch(p.out, ro, sbecodec.DEC_PARSE_MESSAGE, out=s.decoded, seq=s.decoded.seq, in_bytes=288 * m)
+        plan = sbecodec.classify_commits(p.out, ro, dec, table, out=s.plan)
+        f = s.frames
+        fr = sbecodec.emit_commit_offsets(p.out, ro, dec, plan, tid, itab, out=f.out, out_off=f.out_off, status=f.status,
+                                          emit_idx=f.emit_idx, totals=f.totals, workspace=f.workspace, **kw)
+        t0 = int(fr.totals[0])  # host read 2, then the frame table: the frames lie back to back in record order
+        tab = torch.cat([fr.out_off[fr.emit_idx[:t0]], fr.out_off[m: m + 1]])
+        sbecodec.term_append(ing, fr.out, tab, rec_tail=s.appended.rec_tail, counts=s.appended.counts)
+
+    staged()
+    torch.cuda.synchronize()
+    ref = R.sets[0]
+    x = sbecodec.egress_commit_step(ref[0], 0, None, table, tid, idents, torch.empty_like(ref[1]), capacity=cap, **kw)
+    staged_ing = R.sets[(R.k - 1) % len(R.sets)][1]
+    torch.cuda.synchronize()
+    end = int(x.appended.counts[1])
+    assert torch.equal(x.appended.block[:end], staged_ing[:end])  # the two forms write the same ingress bytes
+    ms_s = _wall_ms(staged, steps, warmup)
+    ms_c = _wall_ms(counted, steps, warmup)
+    ms_s2 = _wall_ms(staged, steps, warmup)
+    ev_c = _event_ms(counted, steps, warmup)
+    print(json.dumps({"row": "egress_step_detail", "block_bytes": total, "messages": nmsg, "frames": nmsg,
+                      "ingress_bytes": end, "counted_wall_ms": ms_c, "staged_wall_ms": ms_s, "staged_wall_again_ms": ms_s2,
+                      "counted_event_ms": ev_c, "staged_over_counted": ms_s / ms_c}), flush=True)
+    del R, s0, x, ref
+    torch.cuda.empty_cache()
+
+    # the counted decode beside the sized one
+    n = 1_000_000
+    arena, L, ts = T.fixed256_orders(n)
+    data, off = T.oracle_encode(arena, L, ts)[:2]
+    dd, oo = dev(data, torch.uint8), dev(np.asarray(off, np.uint64), torch.int64)
+    R2 = Rot(lambda k: (dd.clone(), oo.clone(), sbecodec.alloc_decoded(n, "cuda")))
+    full, part = torch.full((1,), n, dtype=torch.int64, device="cuda"), torch.full((1,), n // 16, dtype=torch.int64, device="cuda")
+
+    def sized(m):
+        def fn():
+            d, o, out = R2.next()
+            sbecodec.decode_batch(d, o[: m + 1], sbecodec.DEC_PARSE_MESSAGE, out=out, in_bytes=256 * m)
+        return fn
+
+    def counted_dec(cnt):
+        def fn():
+            d, o, out = R2.next()
+            sbecodec.decode_batch_counted(d, o, cnt, n, sbecodec.DEC_PARSE_MESSAGE, out=out, avg_record_bytes=256)
+        return fn
+
+    ms = {k: _event_ms(f, steps, warmup) for k, f in (("sized_full", sized(n)), ("counted_full", counted_dec(full)),
+                                                      ("sized_full_again", sized(n)), ("sized_sixteenth", sized(n // 16)),
+                                                      ("counted_sixteenth", counted_dec(part)),
+                                                      ("sized_sixteenth_again", sized(n // 16)))}
+    print(json.dumps({"row": "decode_counted_detail", "capacity": n, **{k + "_ms": v for k, v in ms.items()}}), flush=True)
+    line("egress_step", nmsg, ms_c * 1e-3,
+         {"egress_commit_step (one enqueue, wall clock)": (ms_c, 2 * total + nmsg * (288 + DESC) + 2 * end),
+          "staged: the uncounted calls with two host reads (wall clock)": (ms_s, 2 * total + nmsg * (288 + DESC) + 2 * end)})
+
+
 def row_commit_emit(steps, warmup):
     """sbe_emit_commit_offsets over 1 M decoded and classified fixed-256 Orders whose headers all
     carry a known topic (every record emits a session-framed CommitOffsetLite; short identifiers),
@@ -1284,7 +1416,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,order_select,term_scan,term_poll,term_append,commit_emit,commit_fallback,ack_correlate,delivery_track,delivery_report")
+    ap.add_argument("--rows", default="mixed,var,session,lite301,lite201,reassemble,order_json,publish_orders,materialize,autocommit,json_extract,order_select,term_scan,term_poll,term_append,commit_emit,commit_fallback,egress_step,ack_correlate,delivery_track,delivery_report")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
     ap.add_argument("--lib", help="library build to measure (A/B of variants; default: the product's)")
     ap.add_argument("--rotate", type=int, default=3, help="copies of a row's buffers the steps rotate over")
@@ -1327,6 +1459,8 @@ def main():
             row_commit_emit(args.steps, args.warmup)
         elif r == "commit_fallback":
             row_commit_fallback(args.steps, args.warmup)
+        elif r == "egress_step":
+            row_egress_step(args.steps, args.warmup)
         elif r == "ack_correlate":
             row_ack_correlate(args.steps, args.warmup)
         elif r == "delivery_track":
