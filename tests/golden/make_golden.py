@@ -6,6 +6,8 @@ is produced by the reference's own SBE-generated flyweights (include/model/*.h c
 driven in the reference's call order by oracle/ref_flyweights.cpp).  survey_probes.json holds the
 outputs of the reference functions themselves as recorded in SURVEY.md Appendix B (probe runs of
 the compiled reference in the survey container); those expectations are transcribed, not computed.
+parse_ref.json holds what the reference's own src/sbe_encoder.cpp, compiled where it lies into
+oracle/_ref/libsbe_ref_src.so, returns for the hand table of tests/refsrc_lib.py.
 
 Inputs only are derived from tests/sbe_testlib.py generators and tests/sbe_testlib.edge_records().
 """
@@ -143,6 +145,38 @@ def main():
                                "wrapForDecode + topicId + sequence + getXAsString for decode)",
                **lite}, open(os.path.join(HERE, "lite_ref.json"), "w"), indent=1)
     print(f"lite encode {len(lite['encode'])}, lite decode {len(lite['decode'])}")
+    parse = parse_cases()
+    source = ("the reference's own src/sbe_encoder.cpp compiled where it lies (oracle/_ref/libsbe_ref_src.so behind "
+              "oracle/ref_sources.cpp): MessageParser::parse_message of each record of tests/refsrc_lib.hand_table(), "
+              "one row per record in the order of `columns`.  rec: the record as hex.  pred: is_session_event | "
+              "is_topic_message << 1 | is_acknowledgment << 2 | is_order_message << 3 of the result.  desc: "
+              "ParseResult::get_description.  result: the ParseResult's fields in the struct's order (`result_fields`) "
+              "without the run of default values at the end.  A string's bytes are the code points of the JSON "
+              "string (Latin-1).")
+    import golden_lib as G
+    with open(os.path.join(HERE, "parse_ref.json"), "w") as f:  # one case per line
+        f.write('{"source": %s,\n"columns": %s,\n"result_fields": %s,\n"cases": [\n'
+                % (json.dumps(source), json.dumps(G.PARSE_COLUMNS), json.dumps(list(G.PARSE_DEFAULTS))))
+        f.write(",\n".join(json.dumps([c[k] for k in G.PARSE_COLUMNS], separators=(",", ":")) for c in parse))
+        f.write("\n]}\n")
+    print(f"parse {len(parse)}")
+
+
+def parse_cases():
+    """The hand table of tests/refsrc_lib.py with the reference's ParseResult, predicates and
+    description of every record."""
+    import golden_lib as G
+    import refsrc_lib as R
+    if not T.refsrc_available():
+        sys.exit("oracle/_ref/libsbe_ref_src.so is missing: run `make -C oracle` with the reference tree present")
+    cases = []
+    for name, rec in R.hand_table():
+        r, pred = T.ref_parse(rec)
+        assert (r, pred) == T.ref_parse(rec, T.PAD_NOISE), name  # decided by the record's own bytes
+        line = dict(kv.split("=", 1) for kv in T.ref_describe(rec, T.DESC_RESULT).split(" "))
+        cases.append({"name": name, "rec": hx(rec), "result": G.pack_result(r), "pred": pred,
+                      "desc": bytes.fromhex(line["desc"]).decode("latin-1")})
+    return cases
 
 
 def lite_encode_inputs():

@@ -284,6 +284,64 @@ def check_lite_decode(cases, decode):
 
 
 # ------------------------------------------------------------------------------------------
+# parse_ref.json: MessageParser::parse_message of the reference's own compiled source
+# ------------------------------------------------------------------------------------------
+PARSE_DEFAULTS = dict(success=False, error_message=b"", message_type=b"", message_id=b"", payload=b"", headers=b"",
+                      timestamp=0, sequence_number=0, template_id=0, schema_id=0, version=0, block_length=0,
+                      correlation_id=0, session_id=0, leader_member_id=0, event_code=0, leadership_term_id=0)
+
+
+def pack_result(r):
+    """A ParseResult dict as the fixture stores it: its fields in PARSE_DEFAULTS' order (the
+    struct's, success first) without the run of default values at the end, success as 0 / 1; a
+    string's bytes are the code points of the JSON string (Latin-1)."""
+    vals = [r[k].decode("latin-1") if isinstance(dflt, bytes) else int(r[k]) for k, dflt in PARSE_DEFAULTS.items()]
+    dflts = ["" if isinstance(d, bytes) else 0 for d in PARSE_DEFAULTS.values()]
+    while vals and vals[-1] == dflts[len(vals) - 1]:
+        vals.pop()
+    return vals
+
+
+def unpack_result(packed):
+    r = dict(PARSE_DEFAULTS)
+    for (k, dflt), v in zip(PARSE_DEFAULTS.items(), packed):
+        r[k] = v.encode("latin-1") if isinstance(dflt, bytes) else bool(v) if isinstance(dflt, bool) else v
+    return r
+
+
+PARSE_COLUMNS = ["name", "rec", "pred", "desc", "result"]
+
+
+def parse_ref_cases():
+    """parse_ref.json's rows as dicts."""
+    f = load("parse_ref.json")
+    assert f["columns"] == PARSE_COLUMNS and f["result_fields"] == list(PARSE_DEFAULTS)
+    return [dict(zip(PARSE_COLUMNS, row)) for row in f["cases"]]
+
+
+def check_parse_ref(cases, parse):
+    """parse(records) -> (parse-mode descriptors, sequence numbers, sbe_order_select's pred) of the
+    subject for all records as one batch.  Every ParseResult field and the four predicates of every
+    case."""
+    recs = [bytes.fromhex(c["rec"]) for c in cases]
+    dec, seq, pred = parse(recs)
+    for i, c in enumerate(cases):
+        got = T.materialize_parse(recs[i], T.row(dec, i))
+        got["sequence_number"] = int(seq[i])
+        exp = unpack_result(c["result"])
+        assert got == exp, (c["name"], {k: (got[k], exp[k]) for k in exp if got[k] != exp[k]})
+        assert int(pred[i]) == c["pred"], (c["name"], int(pred[i]), c["pred"])
+    return len(cases)
+
+
+def oracle_parse(recs):
+    import select_lib as S
+    data, off = T.pack_records(list(recs))
+    dec = T.oracle_decode(data, off, T.DEC_PARSE)
+    return dec, T.oracle_seq_batch(data, off, dec), S.model(data, off, dec)["pred"]
+
+
+# ------------------------------------------------------------------------------------------
 # the CPU subject: the oracle restatement, one record per call as the reference is called
 # ------------------------------------------------------------------------------------------
 def _pack(fields):

@@ -374,6 +374,107 @@ def _split(raw, flen, k):
 
 
 # ------------------------------------------------------------------------------------------
+# the reference's own codec source (oracle/_ref/libsbe_ref_src.so: src/sbe_encoder.cpp compiled where
+# it lies behind oracle/ref_sources.cpp; only where the reference tree was present to build it)
+# ------------------------------------------------------------------------------------------
+REFSRC_LIB = os.path.join(ORACLE_DIR, "_ref", "libsbe_ref_src.so")
+_refsrc = None
+PAD_ZERO = b"\0" * 65600
+# bytes no valid record continues with, mixed with the texts a read past the record could pick up
+PAD_NOISE = (b"\xff\x7f" * 8 + b'side ORDER "_sequence_number":7 ' + b"\xff\x7f" * 8) * 1026
+PAD_NOISE = PAD_NOISE[:65600]
+PARSE_NUMS = ("success", "timestamp", "sequence_number", "template_id", "schema_id", "version", "block_length",
+              "correlation_id", "session_id", "leader_member_id", "event_code", "leadership_term_id")
+PARSE_STRS = ("error_message", "message_type", "message_id", "payload", "headers")
+
+
+def refsrc_available():
+    return os.path.exists(REFSRC_LIB)
+
+
+def refsrc():
+    global _refsrc
+    if _refsrc is None:
+        L = ctypes.CDLL(REFSRC_LIB)
+        vp, u64, u32, i = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
+        L.refsrc_parse_message.restype = i
+        L.refsrc_parse_message.argtypes = [vp, u64, vp, u64, vp, vp, vp]
+        L.refsrc_classify_topic.restype = i
+        L.refsrc_classify_topic.argtypes = [vp, u64]
+        L.refsrc_encode_topic_message.restype = i
+        L.refsrc_encode_topic_message.argtypes = [vp, vp, ctypes.c_int64, vp, u64, vp, vp, u64]
+        L.refsrc_describe.restype = u64
+        L.refsrc_describe.argtypes = [vp, u64, u32, vp, u64]
+        _refsrc = L
+    return _refsrc
+
+
+def _padded(rec: bytes, pad: bytes):
+    # as _rec_buf: the reference's getXAsString builds its string before the bounds check, so the
+    # bytes behind the record are read (and discarded); they lie inside this allocation
+    return ctypes.create_string_buffer(bytes(rec) + pad, len(rec) + len(pad))
+
+
+def ref_parse(rec: bytes, pad: bytes = PAD_ZERO):
+    """(ParseResult dict with materialize_parse's keys, 4-bit pred as select_lib numbers it) of the
+    reference's MessageParser::parse_message on rec, with `pad` behind it."""
+    b = _padded(rec, pad)
+    cap = 5 * len(rec) + 4096
+    sbuf = ctypes.create_string_buffer(cap)
+    slen = (ctypes.c_uint64 * 5)()
+    nums = (ctypes.c_int64 * 12)()
+    preds = (ctypes.c_uint8 * 4)()
+    rc = refsrc().refsrc_parse_message(b, len(rec), sbuf, cap, slen, nums, preds)
+    assert rc == 0, rc
+    r = dict(zip(PARSE_STRS, _split(sbuf.raw, slen, 5)))
+    r.update(zip(PARSE_NUMS, (int(x) for x in nums)))
+    r["success"] = bool(r["success"])
+    r["sequence_number"] &= 2**64 - 1
+    return r, preds[0] | preds[1] << 1 | preds[2] << 2 | preds[3] << 3
+
+
+def ref_parse_message(rec: bytes) -> dict:
+    return ref_parse(rec)[0]
+
+
+def ref_predicates(rec: bytes) -> int:
+    """PR_SESSION_EVENT | PR_TOPIC_MESSAGE | PR_ACKNOWLEDGMENT | PR_ORDER_MESSAGE bits of the
+    reference's predicates on its own ParseResult of rec."""
+    return ref_parse(rec)[1]
+
+
+def ref_classify_topic(topic: bytes) -> int:
+    b = ctypes.create_string_buffer(bytes(topic), len(topic) + 1)
+    return int(refsrc().refsrc_classify_topic(b, len(topic)))
+
+
+def ref_encode_topic_message(fields, ts):
+    """SBEEncoder::encode_topic_message itself: (0, record) or (1, the exception's text)."""
+    bufs = [ctypes.create_string_buffer(bytes(f), max(len(f), 1)) for f in fields]
+    ptrs = (ctypes.c_void_p * 5)(*[ctypes.addressof(b) for b in bufs])
+    lens = (ctypes.c_uint32 * 5)(*[len(f) for f in fields])
+    cap = 34 + sum(len(f) for f in fields) + 16
+    out, err = ctypes.create_string_buffer(cap), ctypes.create_string_buffer(256)
+    n = ctypes.c_uint64(0)
+    rc = refsrc().refsrc_encode_topic_message(ptrs, lens, int(ts), out, cap, ctypes.byref(n), err, 256)
+    assert rc in (0, 1), rc
+    return rc, out.raw[: n.value] if rc == 0 else err.value
+
+
+DESC_RESULT, DESC_BYTES, DESC_ACK_FOR = 1, 2, 4
+
+
+def ref_describe(rec: bytes, what=DESC_RESULT | DESC_BYTES | DESC_ACK_FOR) -> str:
+    """The canonical line of oracle/parse_line.hpp from the reference's functions."""
+    b = _padded(rec, PAD_ZERO)
+    cap = 16 * len(rec) + 8192
+    out = ctypes.create_string_buffer(cap)
+    n = refsrc().refsrc_describe(b, len(rec), what, out, cap)
+    assert n <= cap
+    return out.raw[:n].decode()
+
+
+# ------------------------------------------------------------------------------------------
 # materialisers: descriptor → reference result objects
 # ------------------------------------------------------------------------------------------
 def _i64(u):

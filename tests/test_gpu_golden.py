@@ -319,3 +319,34 @@ def test_survey_probes(codec, server, how):
     else:
         encode, decode = DevEncode(codec, "serve", server), serve_decode(server)
     assert G.check_survey_probes(PROBES, encode, decode) == 16
+
+
+# ------------------------------------------------------------------------------------------
+# parse_ref.json
+# ------------------------------------------------------------------------------------------
+PARSE = G.parse_ref_cases()
+
+
+@pytest.mark.parametrize("lead", [0, 1, 15])
+def test_parse_ref_cases(codec, lead):
+    """The device as subject: decode_batch with the fused sequence number and sbe_order_select over
+    the fixture's records as one batch behind `lead` bytes."""
+    def parse(recs):
+        data, off = T.pack_records([b"\0" * lead] + list(recs))
+        d, ro = to_dev(data, torch.uint8), to_dev(off, torch.int64)
+        dec = codec.decode_batch(d, ro, mode=codec.DEC_PARSE_MESSAGE, seq=True)
+        pred = codec.order_select(d, ro, dec).numpy()["pred"]
+        torch.cuda.synchronize()
+        return {k: v[1:] for k, v in dec.numpy().items()}, dec.seq.cpu().numpy().view(np.uint64)[1:], pred[1:]
+    assert G.check_parse_ref(PARSE, parse) == len(PARSE) >= 150
+
+
+def test_parse_ref_cases_host_mirror(codec, tmp_path):
+    """The host mirror as subject (tests/cpp/test_parse_lines.cpp, one parse_message call per
+    record): its predicates and ParseResult::get_description against the fixture's."""
+    import refsrc_lib as R
+    lines = R.mirror_lines([bytes.fromhex(c["rec"]) for c in PARSE], "single", tmp_path)
+    for c, ln in zip(PARSE, lines):
+        kv = dict(x.split("=", 1) for x in ln.split(" "))
+        assert bytes.fromhex(kv["desc"]) == c["desc"].encode("latin-1") and int(kv["pred"][::-1], 2) == c["pred"], (c["name"], kv["desc"], kv["pred"])
+        assert kv["ok"] == str(c["result"][0]), c["name"]

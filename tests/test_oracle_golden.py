@@ -2,6 +2,8 @@
 tests/golden/*_ref.json) and the reference probe observations (SURVEY Appendix B,
 tests/golden/survey_probes.json).  Bit-exact.  The expectations are golden_lib's, which
 tests/test_gpu_golden.py runs with the device as subject."""
+import os
+
 import pytest
 
 import golden_lib as G
@@ -52,3 +54,18 @@ def test_on_egress_tm_ack_claims():
 @pytest.mark.parametrize("probe", load("survey_probes.json")["probes"], ids=lambda p: p["name"])
 def test_survey_probe(probe):
     G.check_survey_probe(probe, G.oracle_encode, G.oracle_decode)
+
+
+def test_parse_ref_cases():
+    """parse_ref.json: what the reference's compiled MessageParser::parse_message returned for the
+    hand table of tests/refsrc_lib.py, all 17 ParseResult fields and the four predicates, with the
+    oracle and the predicate model as subject.  The table itself is still the one the fixture was
+    made from, and the fixture holds every outcome but the unreachable one."""
+    import refsrc_lib as R
+    cases = G.parse_ref_cases()
+    assert [(c["name"], c["rec"]) for c in cases] == [(n, r.hex()) for n, r in R.hand_table()]
+    assert G.check_parse_ref(cases, G.oracle_parse) == len(cases) >= 150
+    seen = {R.outcome_class(G.unpack_result(c["result"])) for c in cases}
+    assert seen == set(R.CLASSES) | {R.NULL_EMPTY}
+    assert {c["pred"] for c in cases} >= {0, 1, 2, 6, 10, 14}
+    assert os.path.getsize(os.path.join(G.GOLD, "parse_ref.json")) <= 32 * 1024
